@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- pretraining clips/sec of the VIOLETv2 step on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N --steps K --warmup W --batch B]         (N>1: launched by torch.distributed.run)
+    python bench.py [--gpus N --steps K --warmup W --batch B --dump-outputs DIR]         (N>1: launched by torch.distributed.run)
 
 A "step" = one full optimizer step of the hot path over one synthetic WebVid-shape batch already resident in HBM:
 rm/bm + MLM masking on the device (vmvm_masking, fresh draws each step; --host-masking moves it out of the timed region) ->
@@ -172,6 +172,32 @@ def cpu_baseline(size, frames, timeout_s=600):
     return res
 
 
+DUMP_PER_PARAM = 4096                 # --dump-outputs: elements sampled per parameter tensor (all of a smaller one)
+DUMP_LIMIT = 64 << 20                 # bytes, all files together
+
+
+def dump_outputs(path, store, losses, with_moments):
+    """--dump-outputs: what the last timed step hands its caller -- the losses it returned (loss_<name>.npy, float64) and the model it
+    updated in place: a fixed sample of the parameters (params.npy, float32) and of the Adam first moments that carry its gradients
+    (adam_m.npy, float32; left out under ZeRO-1, where a rank holds only its own shards).  Every parameter tensor, in name order,
+    contributes the same seeded positions from run to run, so two builds compare element for element whatever their arena layout."""
+    rng = np.random.RandomState(0)
+    idx = []
+    for n in sorted(store.index):
+        o, c, _ = store.index[n]
+        idx.append(o + (np.arange(c) if c <= DUMP_PER_PARAM else np.unique(rng.randint(0, c, DUMP_PER_PARAM))))
+    idx = torch.from_numpy(np.concatenate(idx)).to(store.flat.device)
+    arrays = {f"loss_{k}": np.float64(v.item()) for k, v in losses.items()}
+    arrays["params"] = store.flat.index_select(0, idx).cpu().numpy()
+    if with_moments:
+        arrays["adam_m"] = store.m.index_select(0, idx).cpu().numpy()
+    total = sum(np.asarray(v).nbytes for v in arrays.values())
+    assert total <= DUMP_LIMIT, f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT}-byte limit"
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, f"{k}.npy"), np.asarray(v))
+
+
 def K_RELEASES():
     from pytorch_empirical_mvm_amd import kernels as K
     return K.RESERVE_RELEASES
@@ -195,7 +221,11 @@ def main():
     ap.add_argument("--cpu-timed", type=int, default=3)
     ap.add_argument("--cpu-warmup", type=int, default=1)
     ap.add_argument("--fp8", action="store_true", help="BASELINE config 5's fp8 MFMA path: fusion qkv / FFN-in forward GEMMs on e4m3 operands (opt-in; never the headline: C2 is bf16)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the losses and a fixed sample of the updated parameters / Adam "
+                    "moments of the LAST timed step as DIR/<name>.npy (rank 0; same arguments, same inputs: two builds compare output for output)")
     a = ap.parse_args()
+    if a.steps < 1 and not a.cpu_baseline_worker:
+        ap.error("--steps must be at least 1")
     if a.cpu_baseline_worker:
         cpu_baseline_worker(a.size, a.frames, a.threads, timed=a.cpu_timed, warmup=a.cpu_warmup)
         return
@@ -275,6 +305,8 @@ def main():
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = float(t.item())
     last = {k: float(v.item()) for k, v in losses.items()}
+    if a.dump_outputs and rank == 0:                   # before the instrumented step below moves the parameters on
+        dump_outputs(a.dump_outputs, model.engine.store, losses, with_moments=not (agent.comm is not None and agent.comm.zero1))
     # one more step with HIP events around the roofline kernels (outside the timed region: the events themselves cost nothing, the
     # step is the same work).  EVERY rank runs it: the step holds the gradient collectives.
     O = min(B, 4)
