@@ -521,7 +521,6 @@ typedef struct {
   const void* d_out; void* d_x;                                             /* backward: d(x2) in, d(x) out (written) */
   void *dx2c, *du, *dy2, *dx1, *dx1w, *dao, *dqkv, *dxw; float* delta; int32_t* inv_k;
   void* ws_main; int64_t ws_main_bytes; void* ws_side; int64_t ws_side_bytes; int32_t reserve_cus;
-  int32_t table_side;          /* 1: a table-gradient launch of its own (vmvm_attn_bwd_desc.table_phase) goes to the side stream; the caller keeps dao / qkv / lse / delta alive for it */
 } vmvm_swin_block;
 int vmvm_swin_block_fwd(const vmvm_swin_block* b, void* stream);
 int vmvm_swin_block_bwd(const vmvm_swin_block* b, void* stream, void* side_stream, void* fork_event);

@@ -86,38 +86,23 @@ class VioletEngine(SwinMixin, FusionMixin, HeadsMixin, DownstreamMixin):
         return self._idx_cache[key]
 
     def _wgrad_launch(self, fn, operands, sync=False):
-        """run fn(workspace) -- weight-gradient launches -- on the side stream behind everything enqueued so far.  The operands (dY, the
-        saved forward activation, row scales) are marked as in use by that stream (`record_stream`): the caching allocator then holds
-        each block back only until the side stream has passed the launch, so the backward frees memory as the tape unwinds.  (Round 3
-        kept a Python reference to every operand until the join at the end of the backward: ~2 GB per fusion layer at M = 69 120 pinned
-        for the whole backward.)"""
+        """run fn(workspace) -- weight-gradient launches -- on the side stream behind everything enqueued so far; the operands (dY, the
+        saved forward activation, row scales) are held by `_whold` until the side stream has passed the launch, so the backward frees
+        memory as the tape unwinds.  (Round 3 kept a Python reference to every operand until the join at the end of the backward: ~2 GB
+        per fusion layer at M = 69 120 pinned for the whole backward.)"""
         if self.wstream is None or sync:
             fn(None)
             return
         self.wstream.wait_stream(torch.cuda.current_stream())
         with L.on_stream(self.wstream):
             fn(self.workspace_w)
-            if self.sw.wgrad_hold:
-                ev = self._wev_pool.pop() if self._wev_pool else torch.cuda.Event()
-                ev.record()
-        if self.sw.wgrad_hold:
-            # Round 6: the operands are HELD (a Python reference in a FIFO) until the side stream has passed their launch -- one event per
-            # launch, the oldest polled once per launch.  Round 4-5 marked them with `record_stream` instead: every block freed that way
-            # leaves an event in the caching allocator, which polls ALL outstanding ones on EVERY allocation -- torch.empty cost 48 us
-            # per call in the step (8 205 calls, 0.40 s of a 9-step profile: 44 ms of the host's ~65 ms per step, tools/scratch/host_profile.py).
-            held = self._wheld
-            held.append((ev, operands))
-            while held and held[0][0].query():
-                self._wev_pool.append(held.popleft()[0])
-        else:
-            for t in operands:
-                if torch.is_tensor(t) and t.is_cuda:
-                    t.record_stream(self.wstream)
-        self._wpending = True
+        self._whold(operands)
 
     def _whold(self, operands):
-        """weight-gradient launches were just enqueued on the side stream by a block-level call (vmvm_bert_layer_bwd): keep their operands
-        alive until the side stream has passed them (the FIFO of `_wgrad_launch`)"""
+        """weight-gradient launches were just enqueued on the side stream: keep their operands alive (a Python reference in a FIFO)
+        until the side stream has passed them -- one event per launch, the oldest polled once per launch.  (Rounds 4-5 marked them as
+        in use by the side stream in the caching allocator instead: every block freed that way leaves an event there, and the allocator
+        polls ALL outstanding ones on EVERY allocation -- torch.empty cost 48 us per call in the step, 44 ms of the host's ~65 ms per step.)"""
         if self.wstream is None:
             return
         ev = self._wev_pool.pop() if self._wev_pool else torch.cuda.Event()
@@ -129,12 +114,24 @@ class VioletEngine(SwinMixin, FusionMixin, HeadsMixin, DownstreamMixin):
         self._wpending = True
 
     def _fork_event(self):
-        """raw handle of the event vmvm_bert_layer_bwd records on the main stream in front of each side-stream launch"""
+        """raw handle of the event a block-level backward records on the main stream in front of each side-stream launch"""
         ev = getattr(self, "_fork_ev", None)
         if ev is None:
             ev = self._fork_ev = torch.cuda.Event()
             ev.record()                      # (the handle exists from the first record on)
         return ev.cuda_event
+
+    def _block_bwd_streams(self, d, device):
+        """fill the scratch and CU-reservation fields of a block-level backward descriptor (vmvm_bert_layer, vmvm_swin_block) ->
+        (side-stream handle, fork event) for the call; (None, None) without the weight-gradient stream"""
+        wsm = K._WORKSPACE.get(device)
+        d.ws_main, d.ws_main_bytes = L.ptr(wsm), (wsm.numel() if wsm is not None else 0)
+        d.reserve_cus = K.reserve_cus()
+        if self.wstream is None:
+            d.ws_side, d.ws_side_bytes = 0, 0
+            return None, None
+        d.ws_side, d.ws_side_bytes = self.workspace_w.data_ptr(), self.workspace_w.numel()
+        return self.wstream.cuda_stream, self._fork_event()
 
     def _wgrad_join(self):
         """the main stream waits for the weight gradients in flight (before the gradient exchange / norm / AdamW read them)"""

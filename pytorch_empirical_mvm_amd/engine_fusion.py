@@ -13,6 +13,13 @@ from . import swin_index as SI
 from .store import BF16, F32, V, DropScale, _acc, _gout, _h2d, _dev_i32
 
 
+class BertPlan:
+    """One fusion layer's parameter names (pre = the layer's prefix, qn / bn = query, key, value weights / biases, wo / w1 / w2 = the
+    attention-output, intermediate and output dense weights), dropout rates p_h (hidden) / p_a (attention), and for a full layer
+    (FusionMixin._bert_layer_plan) M rows and its draws: Philox offsets off_attn / off_1 / off_2 and the recorded-decision buffer drop_mask."""
+    __slots__ = ("pre", "qn", "bn", "wo", "w1", "w2", "p_h", "p_a", "M", "off_attn", "drop_mask", "off_1", "off_2")
+
+
 class FusionMixin:
     # -------------------------------------------------------------- EncVideo / EncTxt  -> one token pool
     def _drop_on(self, site, train):
@@ -87,6 +94,32 @@ class FusionMixin:
         return out, Lv, hw
 
     # -------------------------------------------------------------- fusion encoder
+    def _bert_layer_names(self, l, train):
+        """fusion layer `l`: parameter names and dropout rates (a BertPlan without its draws)"""
+        P = BertPlan()
+        pre = P.pre = f"trsfr.layer.{l}."
+        P.qn = [pre + f"attention.self.{n}.weight" for n in ("query", "key", "value")]
+        P.bn = [pre + f"attention.self.{n}.bias" for n in ("query", "key", "value")]
+        P.wo, P.w1, P.w2 = pre + "attention.output.dense.weight", pre + "intermediate.dense.weight", pre + "output.dense.weight"
+        P.p_h = CFG.BERT["hidden_dropout"] if train else 0.0
+        P.p_a = CFG.BERT["attn_dropout"] if train else 0.0
+        return P
+
+    def _bert_layer_plan(self, l, nseq, Lq, train, causal_from, att_out):
+        """the names, dropout rates and draws of one full fusion layer, shared by `_bert_layer_block` and `_bert_layer_calls`: the Philox
+        offsets of the attention, attention-output and output dropouts, drawn here in that order, and the buffer the attention forward
+        records its dropout decisions in (read back by both backward kernels; None: they re-evaluate Philox)"""
+        P = self._bert_layer_names(l, train)
+        Hd, nh = self.cfg["hidden"], CFG.BERT["heads"]
+        M = P.M = nseq * Lq
+        P.off_attn = self._next_offset(nseq * nh * Lq * Lq)
+        P.drop_mask = None
+        if P.p_a > 0 and self.store_drop_mask:
+            P.drop_mask = K.attention_drop_mask(nseq, Lq, nh, Hd // nh, 1, P.p_a, self.device, causal_from=causal_from, att_colsum=att_out)
+        P.off_1 = self._next_offset(M * Hd)
+        P.off_2 = self._next_offset(M * Hd)
+        return P
+
     def _bert_layer(self, xv, nseq, Lq, keymask, l, train, causal_from=0, att_out=None):
         if self.sw.block_abi and self.device.type == "cuda":
             return self._bert_layer_block(xv, nseq, Lq, keymask, l, train, causal_from, att_out)
@@ -96,22 +129,17 @@ class FusionMixin:
         """HF BertLayer `l` through the block-level C ABI (include/vmvm.h vmvm_bert_layer; csrc/blocks.hip fills the same per-kernel
         descriptors as `_bert_layer_calls` below, which stays as the statement of the layer and as the other side of the bit-for-bit
         test): one descriptor + one foreign call for the forward (10 launches) and one for the backward (22 launches, the four weight
-        gradients on the engine's second stream).  This function only allocates and names buffers."""
+        gradients on the engine's second stream).  Both start from `_bert_layer_plan`; this one only allocates and names buffers."""
         from . import lib as L
         import ctypes as C
         S, dev = self.store, self.device
-        pre = f"trsfr.layer.{l}."
         Hd, nh, F = self.cfg["hidden"], CFG.BERT["heads"], CFG.BERT["ffn"]
-        qn = [pre + f"attention.self.{n}.weight" for n in ("query", "key", "value")]
-        bn = [pre + f"attention.self.{n}.bias" for n in ("query", "key", "value")]
-        M = nseq * Lq
+        P = self._bert_layer_plan(l, nseq, Lq, train, causal_from, att_out)
+        pre, qn, bn, wo, w1, w2, p_h, p_a, M = P.pre, P.qn, P.bn, P.wo, P.w1, P.w2, P.p_h, P.p_a, P.M
         x = xv.t
-        p_h = CFG.BERT["hidden_dropout"] if train else 0.0
-        p_a = CFG.BERT["attn_dropout"] if train else 0.0
         c8 = self.gelu_code8
         d = L.BertLayer()
         d.nseq, d.L, d.hidden, d.heads, d.ffn = nseq, Lq, Hd, nh, F
-        wo, w1, w2 = pre + "attention.output.dense.weight", pre + "intermediate.dense.weight", pre + "output.dense.weight"
         d.Wqkv, d.Wo, d.W1, d.W2 = S.fused(S.shadow, qn, (3 * Hd, Hd)).data_ptr(), S.b(wo).data_ptr(), S.b(w1).data_ptr(), S.b(w2).data_ptr()
         wqt = S.bt(qn[0])                                   # the fused [H, 3H] transposed copy (query | key | value adjacent), or none
         d.WqkvT = L.ptr(wqt if (wqt is not None and tuple(wqt.shape) == (Hd, 3 * Hd)) else None)
@@ -135,14 +163,7 @@ class FusionMixin:
         d.x, d.qkv, d.ctx, d.lse, d.a, d.x1, d.mean1, d.rstd1 = (t_.data_ptr() for t_ in (x, qkv, ctx, lse, a, x1, mean1, rstd1))
         d.u, d.code8, d.h, d.f, d.x2, d.mean2, d.rstd2 = u.data_ptr(), int(c8), h.data_ptr(), f.data_ptr(), x2.data_ptr(), mean2.data_ptr(), rstd2.data_ptr()
         d.keymask, d.causal_from, d.att_colsum = L.ptr(keymask), causal_from, L.ptr(att_out)
-        # Philox offsets in the order `_bert_layer_calls` draws them
-        d.off_attn = self._next_offset(nseq * nh * Lq * Lq)
-        dmask = None
-        if p_a > 0 and self.store_drop_mask:
-            dmask = K.attention_drop_mask(nseq, Lq, nh, Hd // nh, 1, p_a, dev, causal_from=causal_from, att_colsum=att_out)
-        d.drop_mask = L.ptr(dmask)
-        d.off_1 = self._next_offset(M * Hd)
-        d.off_2 = self._next_offset(M * Hd)
+        d.off_attn, d.drop_mask, d.off_1, d.off_2 = P.off_attn, L.ptr(P.drop_mask), P.off_1, P.off_2
         d.p_hidden, d.p_attn, d.seed = p_h, p_a, self.seed
         x8 = x18 = None
         if self.fp8:
@@ -154,7 +175,7 @@ class FusionMixin:
         L.check(lib.vmvm_bert_layer_fwd(C.byref(d), L.stream()), "bert_layer_fwd")
         out = V(x2)
         # the descriptor holds raw addresses: every forward buffer the backward re-reads must stay referenced until the closure has run
-        saved = (x, qkv, ctx, lse, a, x1, mean1, rstd1, u, h, f, mean2, rstd2, dmask, keymask)
+        saved = (x, qkv, ctx, lse, a, x1, mean1, rstd1, u, h, f, mean2, rstd2, P.drop_mask, keymask)
 
         def bwd():
             assert saved is not None
@@ -167,13 +188,8 @@ class FusionMixin:
             dx = e((M, Hd), device=dev, dtype=BF16) if dx is None else dx
             d.d_out, d.d_x = dg.data_ptr(), dx.data_ptr()
             d.df, d.dfm, d.du, d.dx1, d.da, d.dam, d.dctx, d.dqkv, d.delta = (L.ptr(t_) for t_ in (df, dfm, du, dx1, da, dam, dctx, dqkv, delta))
-            wsm = K._WORKSPACE.get(x.device)
-            d.ws_main, d.ws_main_bytes = L.ptr(wsm), (wsm.numel() if wsm is not None else 0)
-            side = self.wstream
-            d.ws_side, d.ws_side_bytes = (self.workspace_w.data_ptr(), self.workspace_w.numel()) if side is not None else (0, 0)
-            d.reserve_cus = K.reserve_cus()
-            L.check(lib.vmvm_bert_layer_bwd(C.byref(d), L.stream(), side.cuda_stream if side is not None else None,
-                                            self._fork_event() if side is not None else None), "bert_layer_bwd")
+            side, fork = self._block_bwd_streams(d, x.device)
+            L.check(lib.vmvm_bert_layer_bwd(C.byref(d), L.stream(), side, fork), "bert_layer_bwd")
             # the side stream reads these until it has passed the four weight gradients (the main-stream buffers die with this closure)
             self._whold((dfm if dfm is not None else df, h, du, x1, dam if dam is not None else da, ctx, dqkv, x))
             _acc(xv, dx)
@@ -181,41 +197,35 @@ class FusionMixin:
         return out
 
     def _bert_layer_calls(self, xv, nseq, Lq, keymask, l, train, causal_from=0, att_out=None):
+        """HF BertLayer `l` one kernel entry point at a time, from the same plan as `_bert_layer_block`: the statement of the layer and the
+        other side of the bit-for-bit test"""
         S, dev = self.store, self.device
-        pre = f"trsfr.layer.{l}."
         Hd, nh = self.cfg["hidden"], CFG.BERT["heads"]
-        qn = [pre + f"attention.self.{n}.weight" for n in ("query", "key", "value")]
-        bn = [pre + f"attention.self.{n}.bias" for n in ("query", "key", "value")]
+        P = self._bert_layer_plan(l, nseq, Lq, train, causal_from, att_out)
+        pre, qn, bn, p_h, M, o1, o2 = P.pre, P.qn, P.bn, P.p_h, P.M, P.off_1, P.off_2
         Wqkv, Gqkv = S.fused(S.shadow, qn, (3 * Hd, Hd)), S.fused(S.grad, qn, (3 * Hd, Hd))
         bqkv, gbqkv = S.fused(S.flat, bn, (3 * Hd,)), S.fused(S.grad, bn, (3 * Hd,))
-        p_h = CFG.BERT["hidden_dropout"] if train else 0.0
-        p_a = CFG.BERT["attn_dropout"] if train else 0.0
-        M = nseq * Lq
         x = xv.t
         a8 = 1.0 / (self.A8_SCALE * S.W8_SCALE)
         if self.fp8:
             qkv = K.gemm(K.cast_fp8(x, self.A8_SCALE), S.fused8(qn, (3 * Hd, Hd)), bias=bqkv, fp8=True, alpha=a8)
         else:
             qkv = K.gemm(x, Wqkv, bias=bqkv)
-        o_att = self._next_offset(nseq * nh * Lq * Lq)
-        akw = dict(q_off=0, k_off=Hd, v_off=2 * Hd, keymask=keymask, dropout_p=p_a, seed=self.seed, offset=o_att, causal_from=causal_from)
-        if p_a > 0 and self.store_drop_mask:                     # the forward's keep / drop decisions, read back by both backward kernels
-            akw["drop_mask"] = K.attention_drop_mask(nseq, Lq, nh, Hd // nh, 1, p_a, dev, causal_from=causal_from, att_colsum=att_out)
+        akw = dict(q_off=0, k_off=Hd, v_off=2 * Hd, keymask=keymask, dropout_p=P.p_a, seed=self.seed, offset=P.off_attn, causal_from=causal_from,
+                   drop_mask=P.drop_mask)
         ctx, lse = K.attention_fwd(qkv, nseq, Lq, nh, Hd // nh, 1, 1.0 / math.sqrt(Hd // nh), att_colsum=att_out, **akw)
-        o1 = self._next_offset(M * Hd)
-        a = K.gemm(ctx, S.b(pre + "attention.output.dense.weight"), bias=S.p(pre + "attention.output.dense.bias"), resid=x,
+        a = K.gemm(ctx, S.b(P.wo), bias=S.p(pre + "attention.output.dense.bias"), resid=x,
                    dropout_p=p_h, seed=self.seed, offset=o1)
         g1, b1 = S.p(pre + "attention.output.LayerNorm.weight"), S.p(pre + "attention.output.LayerNorm.bias")
         x1, mean1, rstd1 = K.layernorm_fwd(a, g1, b1, CFG.BERT["eps"])
         c8 = self.gelu_code8                                     # GELU' saved as an 8-bit code (as in the Swin MLPs)
         u = torch.empty((M, CFG.BERT["ffn"]), device=dev, dtype=torch.uint8 if c8 else BF16)
         if self.fp8:
-            h = K.gemm(K.cast_fp8(x1, self.A8_SCALE), S.b8(pre + "intermediate.dense.weight"), bias=S.p(pre + "intermediate.dense.bias"),
+            h = K.gemm(K.cast_fp8(x1, self.A8_SCALE), S.b8(P.w1), bias=S.p(pre + "intermediate.dense.bias"),
                        act=1, out_preact=u, fp8=True, alpha=a8, code8=c8)
         else:
-            h = K.gemm(x1, S.b(pre + "intermediate.dense.weight"), bias=S.p(pre + "intermediate.dense.bias"), act=1, out_preact=u, code8=c8)
-        o2 = self._next_offset(M * Hd)
-        f = K.gemm(h, S.b(pre + "output.dense.weight"), bias=S.p(pre + "output.dense.bias"), resid=x1, dropout_p=p_h, seed=self.seed, offset=o2)
+            h = K.gemm(x1, S.b(P.w1), bias=S.p(pre + "intermediate.dense.bias"), act=1, out_preact=u, code8=c8)
+        f = K.gemm(h, S.b(P.w2), bias=S.p(pre + "output.dense.bias"), resid=x1, dropout_p=p_h, seed=self.seed, offset=o2)
         g2, b2 = S.p(pre + "output.LayerNorm.weight"), S.p(pre + "output.LayerNorm.bias")
         x2, mean2, rstd2 = K.layernorm_fwd(f, g2, b2, CFG.BERT["eps"])
         out = V(x2)
@@ -224,12 +234,12 @@ class FusionMixin:
             df, dfm = K.layernorm_bwd(out.g, f, g2, mean2, rstd2, S.g(pre + "output.LayerNorm.weight"), S.g(pre + "output.LayerNorm.bias"),
                                       want_dX2=p_h > 0, dropout_p=p_h, seed=self.seed, offset=o2)
             dfm = df if dfm is None else dfm
-            du = self._linear_bwd(dfm, h, pre + "output.dense.weight", pre + "output.dense.bias", dx_kw=dict(act=3, aux=u, code8=c8))
-            dx1 = self._linear_bwd(du, x1, pre + "intermediate.dense.weight", pre + "intermediate.dense.bias", dx_kw=dict(resid=df))
+            du = self._linear_bwd(dfm, h, P.w2, pre + "output.dense.bias", dx_kw=dict(act=3, aux=u, code8=c8))
+            dx1 = self._linear_bwd(du, x1, P.w1, pre + "intermediate.dense.bias", dx_kw=dict(resid=df))
             da, dam = K.layernorm_bwd(dx1, a, g1, mean1, rstd1, S.g(pre + "attention.output.LayerNorm.weight"),
                                       S.g(pre + "attention.output.LayerNorm.bias"), want_dX2=p_h > 0, dropout_p=p_h, seed=self.seed, offset=o1)
             dam = da if dam is None else dam
-            dctx = self._linear_bwd(dam, ctx, pre + "attention.output.dense.weight", pre + "attention.output.dense.bias")
+            dctx = self._linear_bwd(dam, ctx, P.wo, pre + "attention.output.dense.bias")
             dqkv = K.attention_bwd(dctx, qkv, ctx, lse, nseq, Lq, nh, Hd // nh, 1, 1.0 / math.sqrt(Hd // nh), **akw)
             dx = self._linear_bwd(dqkv, x, None, None, w=Wqkv, gw=Gqkv, gb=gbqkv, dx_kw=dict(resid=da, out=_gout(xv)), wT=S.bt(qn[0]))
             _acc(xv, dx)
@@ -244,16 +254,13 @@ class FusionMixin:
         both dense layers, the FFN and both LayerNorms run on nseq rows instead of nseq * Lq.  Same arithmetic per row as
         `_bert_layer`; returns V([nseq, H])."""
         S, dev = self.store, self.device
-        pre = f"trsfr.layer.{l}."
         Hd, nh = self.cfg["hidden"], CFG.BERT["heads"]
         hd = Hd // nh
-        qn = [pre + f"attention.self.{n}.weight" for n in ("query", "key", "value")]
-        bn = [pre + f"attention.self.{n}.bias" for n in ("query", "key", "value")]
+        P = self._bert_layer_names(l, train)
+        pre, qn, bn, p_h, p_a = P.pre, P.qn, P.bn, P.p_h, P.p_a
         Wqkv, Gqkv = S.fused(S.shadow, qn, (3 * Hd, Hd)), S.fused(S.grad, qn, (3 * Hd, Hd))
         bqkv, gbqkv = S.fused(S.flat, bn, (3 * Hd,)), S.fused(S.grad, bn, (3 * Hd,))
         WT = S.bt(qn[0])                                                  # fused W^T [H, 3H] (or None)
-        p_h = CFG.BERT["hidden_dropout"] if train else 0.0
-        p_a = CFG.BERT["attn_dropout"] if train else 0.0
         scale = 1.0 / math.sqrt(hd)
         x = xv.t                                                          # [nseq * Lq, H]
         rows = self._cached(("qrow", nseq, Lq, qpos), lambda: _dev_i32(np.arange(nseq) * Lq + qpos, dev))
@@ -263,14 +270,14 @@ class FusionMixin:
         o_att = self._next_offset(nseq * nh * Lq)
         ctx, pr, prd = K.attn_query_row_fwd(q, kv, nseq, Lq, nh, hd, scale, k_off=0, v_off=Hd, keymask=keymask, dropout_p=p_a, seed=self.seed, offset=o_att)
         o1 = self._next_offset(nseq * Hd)
-        a = K.gemm(ctx, S.b(pre + "attention.output.dense.weight"), bias=S.p(pre + "attention.output.dense.bias"), resid=xc,
+        a = K.gemm(ctx, S.b(P.wo), bias=S.p(pre + "attention.output.dense.bias"), resid=xc,
                    dropout_p=p_h, seed=self.seed, offset=o1)
         g1, b1 = S.p(pre + "attention.output.LayerNorm.weight"), S.p(pre + "attention.output.LayerNorm.bias")
         x1, mean1, rstd1 = K.layernorm_fwd(a, g1, b1, CFG.BERT["eps"])
         u = torch.empty((nseq, CFG.BERT["ffn"]), device=dev, dtype=BF16)
-        h = K.gemm(x1, S.b(pre + "intermediate.dense.weight"), bias=S.p(pre + "intermediate.dense.bias"), act=1, out_preact=u)
+        h = K.gemm(x1, S.b(P.w1), bias=S.p(pre + "intermediate.dense.bias"), act=1, out_preact=u)
         o2 = self._next_offset(nseq * Hd)
-        f = K.gemm(h, S.b(pre + "output.dense.weight"), bias=S.p(pre + "output.dense.bias"), resid=x1, dropout_p=p_h, seed=self.seed, offset=o2)
+        f = K.gemm(h, S.b(P.w2), bias=S.p(pre + "output.dense.bias"), resid=x1, dropout_p=p_h, seed=self.seed, offset=o2)
         g2, b2 = S.p(pre + "output.LayerNorm.weight"), S.p(pre + "output.LayerNorm.bias")
         x2, mean2, rstd2 = K.layernorm_fwd(f, g2, b2, CFG.BERT["eps"])
         out = V(x2)
@@ -279,12 +286,12 @@ class FusionMixin:
             df, dfm = K.layernorm_bwd(out.g, f, g2, mean2, rstd2, S.g(pre + "output.LayerNorm.weight"), S.g(pre + "output.LayerNorm.bias"),
                                       want_dX2=p_h > 0, dropout_p=p_h, seed=self.seed, offset=o2)
             dfm = df if dfm is None else dfm
-            du = self._linear_bwd(dfm, h, pre + "output.dense.weight", pre + "output.dense.bias", dx_kw=dict(act=3, aux=u))
-            dx1 = self._linear_bwd(du, x1, pre + "intermediate.dense.weight", pre + "intermediate.dense.bias", dx_kw=dict(resid=df))
+            du = self._linear_bwd(dfm, h, P.w2, pre + "output.dense.bias", dx_kw=dict(act=3, aux=u))
+            dx1 = self._linear_bwd(du, x1, P.w1, pre + "intermediate.dense.bias", dx_kw=dict(resid=df))
             da, dam = K.layernorm_bwd(dx1, a, g1, mean1, rstd1, S.g(pre + "attention.output.LayerNorm.weight"),
                                       S.g(pre + "attention.output.LayerNorm.bias"), want_dX2=p_h > 0, dropout_p=p_h, seed=self.seed, offset=o1)
             dam = da if dam is None else dam
-            dctx = self._linear_bwd(dam, ctx, pre + "attention.output.dense.weight", pre + "attention.output.dense.bias")
+            dctx = self._linear_bwd(dam, ctx, P.wo, pre + "attention.output.dense.bias")
             dq, dkv = K.attn_query_row_bwd(dctx, q, kv, pr, prd, nseq, Lq, nh, hd, scale, k_off=0, v_off=Hd)
             # query projection: d(xc) = dq Wq + da (the residual of the attention block); key / value projection: d(x) = dkv Wkv
             dxc = self._linear_bwd(dq, xc, None, None, w=Wqkv[:Hd], gw=Gqkv[:Hd], gb=gbqkv[:Hd], dx_kw=dict(resid=da),

@@ -106,7 +106,7 @@ class SwinBlock(C.Structure):
                 ("map_m", c_void_p), ("x2", c_void_p), ("d_out", c_void_p), ("d_x", c_void_p), ("dx2c", c_void_p), ("du", c_void_p),
                 ("dy2", c_void_p), ("dx1", c_void_p), ("dx1w", c_void_p), ("dao", c_void_p), ("dqkv", c_void_p), ("dxw", c_void_p),
                 ("delta", c_void_p), ("inv_k", c_void_p), ("ws_main", c_void_p), ("ws_main_bytes", c_i64), ("ws_side", c_void_p),
-                ("ws_side_bytes", c_i64), ("reserve_cus", c_int), ("table_side", c_int)]
+                ("ws_side_bytes", c_i64), ("reserve_cus", c_int)]
 
 
 class AdamWDesc(C.Structure):

@@ -592,54 +592,3 @@ def test_block_level_swin_block_equals_the_per_kernel_calls_bit_for_bit():
     nd = int((ga != gb).sum())
     print(f"\n[swin block ABI] schedules {sorted(seen)}; losses {la}; gradient entries that differ: {nd} of {ga.numel()}")
     assert float(ga.abs().max()) > 0 and nd == 0, nd
-
-
-@pytest.mark.timeout(900)
-def test_streaming_window_table_gradient_on_the_second_stream_equals_the_in_line_launch():
-    """Config-5 geometry ((8,12,12) windows = 1 152 tokens: the streaming attention kernels, whose bias-table gradient is a launch of
-    its own).  `vmvm_attn_bwd_desc.table_phase` splits the backward so that launch runs on the second stream beside the GEMMs that
-    follow (VMVM_TABLE_SIDE, opt-in: the config-5 step measured 1.4-3 % SLOWER with it -- the chip is saturated either way), through the block-level call and through the per-kernel calls.  Against the in-line order:
-    every gradient that is not a table gradient identical bit for bit, the table gradients (f32 atomics in that kernel, either way)
-    equal to rounding."""
-    model, args = _engine(dict(vis_backbone_size="large", size_frame=16, max_size_frame=16, size_img=384, max_iter=100, seed=88))
-    import sys
-    sys.path.insert(0, os.path.join(os.path.dirname(__file__), ".."))
-    import bench
-    from pytorch_empirical_mvm_amd.agent import Agent_Pretrain
-    agent = Agent_Pretrain(args, model)
-    img, txt, mask = bench.synth_batch(args, 2, "cuda", 123)
-    import random
-    random.seed(5); np.random.seed(5); torch.manual_seed(5)
-    mb = agent.prepare_batch(agent.masking(img, txt, mask, None))
-    model.eval()
-    eng, S = model.engine, model.engine.store
-    assert eng.wstream is not None
-    b = dict(img=mb["unmask_img"].float().contiguous(), cov=mb["cov"].contiguous(), txt=mb["txt"], mask=mb["mask"], ans_mtm=mb["ans_mtm"])
-    from pytorch_empirical_mvm_amd import kernels as K
-    assert K.attention_table_separate(8 * 12 * 12, 0) and not K.attention_table_separate(392, 0)
-    res = {}
-    saved = (eng.sw.table_side, eng.sw.block_abi)
-    try:
-        for mode in ((False, True), (True, True), (True, False)):
-            eng.sw.table_side, eng.sw.block_abi = mode
-            eng.rng_offset = 0
-            S.grad.zero_()
-            losses, _ = eng.forward_backward(b, negatives=np.array([[1], [0]]), train=False, backward=True)
-            torch.cuda.synchronize()
-            res[mode] = S.grad[:S.n_trainable].clone()
-    finally:
-        eng.sw.table_side, eng.sw.block_abi = saved
-    ref = res[(False, True)]
-    tab = torch.zeros_like(ref, dtype=torch.bool)
-    n_tab = 0
-    for nm, ent in S.index.items():
-        if nm.endswith("relative_position_bias_table") and ent[0] + ent[1] <= S.n_trainable:
-            tab[ent[0]:ent[0] + ent[1]] = True
-            n_tab += 1
-    assert n_tab == 24 and float(ref[tab].abs().max()) > 0
-    for mode in ((True, True), (True, False)):
-        g = res[mode]
-        assert torch.equal(g[~tab], ref[~tab]), mode
-        err = float((g[tab] - ref[tab]).abs().max() / ref[tab].abs().max())
-        print(f"\n[table gradient on the second stream, block_abi={mode[1]}] max |difference| / max |table gradient| = {err:.2e}")
-        assert err < 1e-5, (mode, err)
