@@ -473,7 +473,8 @@ typedef struct {
   void* qkv;                                     /* [M][3H] */
   void* ctx; float* lse;                         /* [M][H], f32 [nseq][heads][L] */
   void* a; void* x1; float *mean1, *rstd1;       /* attention block: dense + dropout + residual, its LayerNorm */
-  void* u; int32_t code8;                        /* saved for the GELU backward: uint8 GELU' codes (code8 = 1) or the bf16 pre-activation, [M][F] */
+  void* u; int32_t code8;                        /* saved for the GELU backward: uint8 GELU' codes (code8 = 1) or the bf16 pre-activation, [M][F];
+                                                  * NULL: inference form, nothing saved (vmvm_bert_layer_bwd refuses it) */
   void* h; void* f; void* x2; float *mean2, *rstd2;   /* FFN: GELU(fc1) [M][F], fc2 + dropout + residual, output LayerNorm = the layer's output */
   const uint8_t* keymask; int32_t causal_from; float* att_colsum; void* drop_mask;      /* as vmvm_attn_fwd_desc */
   float p_hidden, p_attn; uint64_t seed, off_attn, off_1, off_2;                        /* dropout (0 = off) and Philox offsets */
@@ -524,6 +525,18 @@ typedef struct {
 } vmvm_swin_block;
 int vmvm_swin_block_fwd(const vmvm_swin_block* b, void* stream);
 int vmvm_swin_block_bwd(const vmvm_swin_block* b, void* stream, void* side_stream, void* fork_event);
+
+/* Full-corpus text-to-video retrieval evaluation (eval_retrieval.py:100-115, eval_retrieval_tsv.py:53-91; csrc/retrieval.hip).
+ * clip mean: dst[b][r][:] = mean_c src[b][c][r][:] of bf16 [B][clips][rows][H] (f32 sums) -> bf16 [B][rows][H] (the video bank rows) */
+int vmvm_clip_mean_bf16(const void* src, void* dst, int32_t B, int32_t clips, int32_t rows, int32_t H, void* stream);
+/* pair block: texts [t0, t0+nt) x videos [v0, v0+nv), pair p = t*nv + v -> seq bf16 [P][Lv+X][H] = [vid_bank rows of video v0+v ;
+ * txt_bank rows of text t0+t] and keymask u8 [P][Lv+X] = [ones ; txt_mask row != 0].  vid_bank bf16 [Nv][Lv][H], txt_bank bf16
+ * [Nt][X][H], txt_mask u8 [Nt][X]; the block must lie inside both banks */
+int vmvm_retrieval_assemble(const void* vid_bank, int32_t Nv, int32_t Lv, const void* txt_bank, const uint8_t* txt_mask, int32_t Nt,
+                            int32_t X, int32_t H, int32_t t0, int32_t nt, int32_t v0, int32_t nv, void* seq, uint8_t* keymask, void* stream);
+/* scores f32 [Nt][ld] (fc logits in, sigmoid out, in place); rank[t] = 1-based position of video gt[t] after a stable sort of row t by
+ * descending score = 1 + #{v : s > s_gt} + #{v < gt : s == s_gt} (-1 when gt[t] is outside [0, Nv)); one workgroup per row */
+int vmvm_retrieval_rank(float* scores, int32_t Nt, int32_t Nv, int32_t ld, const int32_t* gt, int32_t* rank, void* stream);
 
 /* hardware probe used by tests: dumps the lane mapping of ds_read_b64_tr_b16 (out: 64*4 int32) */
 int vmvm_probe_tr16(int32_t* out, void* stream);

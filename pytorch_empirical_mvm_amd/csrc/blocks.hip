@@ -43,7 +43,7 @@ int check(const vmvm_bert_layer* l) {
   if (!l || l->nseq <= 0 || l->L <= 0 || l->hidden <= 0 || l->heads <= 0 || l->ffn <= 0 || (l->hidden % l->heads) || (l->hidden & 7) || (l->ffn & 7)) return VMVM_EINVAL;
   if ((int64_t)l->nseq * l->L > 0x7fffffff / 4) return VMVM_ENOSUPPORT;
   if (!l->Wqkv || !l->Wo || !l->W1 || !l->W2 || !l->bqkv || !l->bo || !l->b1 || !l->b2 || !l->ln1_g || !l->ln1_b || !l->ln2_g || !l->ln2_b) return VMVM_EINVAL;
-  if (!l->x || !l->qkv || !l->ctx || !l->lse || !l->a || !l->x1 || !l->mean1 || !l->rstd1 || !l->u || !l->h || !l->f || !l->x2 || !l->mean2 || !l->rstd2) return VMVM_EINVAL;
+  if (!l->x || !l->qkv || !l->ctx || !l->lse || !l->a || !l->x1 || !l->mean1 || !l->rstd1 || !l->h || !l->f || !l->x2 || !l->mean2 || !l->rstd2) return VMVM_EINVAL;
   if (l->p_hidden < 0.f || l->p_hidden >= 1.f || l->p_attn < 0.f || l->p_attn >= 1.f) return VMVM_EINVAL;
   if (l->in_fp8 && (!l->Wqkv8 || !l->W18 || !l->x8 || !l->x18 || l->a8_scale <= 0.f || l->w8_scale <= 0.f)) return VMVM_EINVAL;
   return VMVM_OK;
@@ -128,14 +128,14 @@ extern "C" int vmvm_bert_layer_fwd(const vmvm_bert_layer* l, void* stream) {
     RC(vmvm_gemm_bf16(&d, stream));
     RC(ln_fwd(l, l->a, l->x1, l->ln1_g, l->ln1_b, l->mean1, l->rstd1, M, H, stream));
   }
-  if (l->in_fp8) {                                      // BertIntermediate: dense + GELU (+ what the GELU backward needs)
+  if (l->in_fp8) {                                      // BertIntermediate: dense + GELU (+ what the GELU backward needs; u = NULL: inference, no store)
     RC(vmvm_cast_bf16_to_fp8(l->x1, l->x18, (int64_t)M * H, l->a8_scale, stream));
     vmvm_gemm_desc d = gemm0(l->x18, H, l->W18, H, l->h, F, M, F, H, l->reserve_cus);
-    d.bias = l->b1; d.act = 1; d.C2 = l->u; d.ldc2 = F; d.aux_code8 = l->code8; d.in_fp8 = 1; d.alpha = 1.0f / (l->a8_scale * l->w8_scale);
+    d.bias = l->b1; d.act = 1; d.C2 = l->u; d.ldc2 = l->u ? F : 0; d.aux_code8 = l->code8; d.in_fp8 = 1; d.alpha = 1.0f / (l->a8_scale * l->w8_scale);
     RC(vmvm_gemm_bf16(&d, stream));
   } else {
     vmvm_gemm_desc d = gemm0(l->x1, H, l->W1, H, l->h, F, M, F, H, l->reserve_cus);
-    d.bias = l->b1; d.act = 1; d.C2 = l->u; d.ldc2 = F; d.aux_code8 = l->code8;
+    d.bias = l->b1; d.act = 1; d.C2 = l->u; d.ldc2 = l->u ? F : 0; d.aux_code8 = l->code8;
     RC(vmvm_gemm_bf16(&d, stream));
   }
   {                                                     // BertOutput: dense + dropout + residual, LayerNorm
@@ -150,6 +150,7 @@ extern "C" int vmvm_bert_layer_fwd(const vmvm_bert_layer* l, void* stream) {
 
 extern "C" int vmvm_bert_layer_bwd(const vmvm_bert_layer* l, void* stream, void* side_stream, void* fork_event) {
   RC(check(l));
+  if (!l->u) return VMVM_EINVAL;                        // the GELU backward reads what the forward saved there
   if (!l->d_out || !l->d_x || !l->df || !l->du || !l->dx1 || !l->da || !l->dctx || !l->dqkv || !l->delta) return VMVM_EINVAL;
   if (l->p_hidden > 0.f && (!l->dfm || !l->dam)) return VMVM_EINVAL;
   if (!l->gWqkv || !l->gWo || !l->gW1 || !l->gW2 || !l->gbqkv || !l->gbo || !l->gb1 || !l->gb2 || !l->gln1_g || !l->gln1_b || !l->gln2_g || !l->gln2_b) return VMVM_EINVAL;

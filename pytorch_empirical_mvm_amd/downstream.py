@@ -1,6 +1,9 @@
 """Downstream fine-tuning heads on the accelerated encoders.
 * Text-to-video retrieval: `VIOLET_Retrieval` / `Agent_Retrieval` (main_retrieval.py:56-110, NormSoftmaxLoss agent.py:34-50) -- the
   batch's B x B (video, text) pairs are B*B gathered sequences of one fusion pass.
+* Full-corpus text-to-video retrieval evaluation: `VIOLET_RetrievalEval` (eval_retrieval.py:100-115, eval_retrieval_tsv.py:43-91) --
+  banks of clip-averaged video features and text features, every (text, video) pair of the corpus through the fusion encoder on the
+  device, R@1/5/10 and the median rank.
 * Open-ended video QA: `VIOLET_QAOE` / `Agent_QAOE` (main_qaoe.py:42-90) -- one (video, question) pass, classification over the
   answer vocabulary on the text [CLS] state.
 * Multiple-choice video QA, MLM-head form: `VIOLET_QAMC_MLM_Head` / `Agent_QAMC_MLM_Head` (main_qamc_tsv_mlm_head.py:61-123) -- one
@@ -15,6 +18,7 @@ import torch
 
 from . import config as CFG
 from .agent import Agent_Pretrain
+from .engine_downstream import RETRIEVAL_MAX_ROWS, retrieval_metrics
 from .model import VIOLET_Pretrain
 
 
@@ -52,6 +56,73 @@ class Agent_Retrieval(Agent_Pretrain):
             return float(loss.item())
         _, scores = eng.retrieval_forward_backward(img, txt, mask, train=False, backward=False)
         return float((scores.argmax(1) == torch.arange(img.shape[0], device=dev)).float().mean().item())
+
+
+def build_retrieval_banks(tids, vids):
+    """eval_retrieval_tsv.py:53-58 over the items of the evaluation in dataset order: one video bank entry per distinct video id (the
+    first occurrence wins, order of first appearance) and one text bank entry per text id (order of first appearance, the last
+    occurrence's features: a dict assignment).  -> (video ids, text ids, item index of each video entry, item index of each text entry)"""
+    vid_ids, vid_item, tid_pos, tid_item = [], [], {}, []
+    seen = set()
+    for i, (t, v) in enumerate(zip(tids, vids)):
+        if v not in seen:
+            seen.add(v)
+            vid_ids.append(v)
+            vid_item.append(i)
+        if t in tid_pos:
+            tid_item[tid_pos[t]] = i
+        else:
+            tid_pos[t] = len(tid_item)
+            tid_item.append(i)
+    return vid_ids, list(tid_pos), vid_item, tid_item
+
+
+class VIOLET_RetrievalEval(VIOLET_Retrieval):
+    """eval_retrieval.py:100-115: the retrieval model (same parameters and checkpoint keys as `VIOLET_Retrieval`) with the two inference
+    forms of the reference's evaluation, always in eval mode, and `evaluate_corpus`, the loop of eval_retrieval_tsv.py:43-91 with
+    the pair phase on the device.  Features are the engine's bf16 rows."""
+
+    @torch.no_grad()
+    def forward(self, typ, img=None, txt=None, mask=None, feat_img=None, mask_img=None, feat_txt=None, mask_txt=None):
+        """typ 'feat': img (B, Clips, T, 3, H, W), txt / mask (B, X) -> (feat_img (B, Lv, H) = mean over the clips, mask_img (B, Lv) of
+        clip 0 (ones), feat_txt (B, X, H), mask_txt).  typ 'cross': B aligned (video, text) pairs -> fc logits before the sigmoid,
+        `.squeeze()`d as the reference does."""
+        eng = self.engine
+        if typ == "feat":
+            vid, trows, _ = eng.retrieval_encode_bank(img, txt, mask)
+            B, Lv = vid.shape[0], vid.shape[1]
+            return vid, torch.ones(B, Lv, dtype=torch.long, device=eng.device), trows, mask.to(eng.device)
+        if typ == "cross":
+            return eng.retrieval_cross(feat_img, mask_img, feat_txt, mask_txt).squeeze()
+        raise ValueError(f"typ must be 'feat' or 'cross', got {typ!r}")
+
+    @torch.no_grad()
+    def evaluate_corpus(self, batches, gt_txt2vid, max_rows=RETRIEVAL_MAX_ROWS):
+        """eval_retrieval_tsv.py:43-91.  batches: iterable of (img (B, Clips, T, 3, H, W), txt (B, X), mask (B, X), tid (B), vid (B)) as
+        the reference's loader yields them; gt_txt2vid: text id -> its video id.  The banks follow `build_retrieval_banks`; every
+        (text, video) pair of the banks is scored on the device (engine.retrieval_corpus_scores).
+        -> dict(metrics = {'r@1', 'r@5', 'r@10', 'median'} strings as the reference prints them, scores = sigmoid scores f32 (Nt, Nv)
+        on the device, ranks = int32 [Nt], txt_ids / vid_ids = the bank orders of the rows / columns)"""
+        eng = self.engine
+        vrows, trows, tmask, tids, vids = [], [], [], [], []
+        for img, txt, mask, tid, vid in batches:
+            fv, ft, km = eng.retrieval_encode_bank(img, txt, mask)
+            ft = ft.clone()                                # (a view of the batch's token pool: keep the text rows only)
+            for b in range(fv.shape[0]):
+                vrows.append(fv[b])
+                trows.append(ft[b])
+                tmask.append(km[b])
+            tids += [int(t) if torch.is_tensor(t) else t for t in tid]
+            vids += [v.item() if torch.is_tensor(v) else v for v in vid]
+        vid_ids, txt_ids, vid_item, tid_item = build_retrieval_banks(tids, vids)
+        vid_bank = torch.stack([vrows[i] for i in vid_item])
+        txt_bank = torch.stack([trows[i] for i in tid_item])
+        txt_mask = torch.stack([tmask[i] for i in tid_item])
+        del vrows, trows, tmask
+        vpos = {v: i for i, v in enumerate(vid_ids)}
+        gt = [vpos[gt_txt2vid[t]] for t in txt_ids]
+        scores, ranks = eng.retrieval_corpus_scores(vid_bank, txt_bank, txt_mask, gt, max_rows=max_rows)
+        return dict(metrics=retrieval_metrics(ranks.tolist()), scores=scores, ranks=ranks, txt_ids=txt_ids, vid_ids=vid_ids)
 
 
 class VIOLET_QAOE(VIOLET_Pretrain):

@@ -10,7 +10,42 @@ import torch
 from . import config as CFG
 from . import kernels as K
 from . import swin_index as SI
-from .store import BF16, F32, V, DropScale, _acc, _gout, _h2d, _dev_i32
+from .store import BF16, F32, V, DropScale, NoTape, _acc, _gout, _h2d, _dev_i32
+
+RETRIEVAL_MAX_ROWS = 1 << 18            # default cap of P * Lq, the fusion rows of one block of the corpus evaluation
+
+
+def plan_retrieval_blocks(Nt, Nv, Lq, max_rows=RETRIEVAL_MAX_ROWS):
+    """Blocks (t0, nt, v0, nv) of the (Nt, Nv) pair grid for `retrieval_corpus_scores`: nt texts x all Nv videos when one text row fits
+    (Nv * Lq <= max_rows), else one text x a range of nv videos (the ranges of a row as even as the cap allows).  Either way the pairs
+    p = t * nv + v of a block are one contiguous run [t0 * Nv + v0, + nt * nv) of the row-major score matrix, and nt * nv * Lq <= max_rows."""
+    if min(Nt, Nv, Lq) <= 0:
+        raise ValueError(f"empty corpus or sequence: Nt={Nt} Nv={Nv} Lq={Lq}")
+    if Lq > max_rows:
+        raise ValueError(f"max_rows={max_rows} is below one fusion sequence (Lq={Lq})")
+    if Nv * Lq <= max_rows:
+        nt = max_rows // (Nv * Lq)
+        return [(t0, min(nt, Nt - t0), 0, Nv) for t0 in range(0, Nt, nt)]
+    per = max_rows // Lq                                   # videos of one block at most
+    nv = -(-Nv // -(-Nv // per))                           # the same number of blocks per row, sized evenly
+    return [(t, 1, v0, min(nv, Nv - v0)) for t in range(Nt) for v0 in range(0, Nv, nv)]
+
+
+def retrieval_metrics(ranks):
+    """eval_retrieval_tsv.py:79-91: the reference's dict of strings from the 1-based ground-truth ranks of the text queries -- recalls
+    accumulated as 1 / n per hit and printed "%.2f" after * 100, `median` = int(np.median(ranks)) (an even count truncates the .5)"""
+    ranks = [int(p) for p in ranks]
+    if not ranks:
+        raise ValueError("no queries")
+    n = len(ranks)
+    res = {"r@1": 0, "r@5": 0, "r@10": 0}
+    for p in ranks:
+        for k in (1, 5, 10):
+            if p <= k:
+                res[f"r@{k}"] += 1.0 / n
+    out = {k: f"{v * 100:.2f}" for k, v in res.items()}
+    out["median"] = f"{int(np.median(ranks))}"
+    return out
 
 
 class DownstreamMixin:
@@ -102,6 +137,78 @@ class DownstreamMixin:
         dh = K.rowdot_bwd(st["h"], S.p("fc.3.weight", (2 * Hd,)), dlg, inv_temp, S.g("fc.3.weight", (2 * Hd,)), S.g("fc.3.bias"), relu_mask=True)
         self._finish_pass(fz, pool, self._cls_hidden_bwd(st, dh))
         return loss, scores
+
+    # -------------------------------------------------------------- downstream: full-corpus retrieval evaluation (eval_retrieval_tsv.py)
+    @torch.no_grad()
+    def retrieval_encode_bank(self, img, txt, mask):
+        """VIOLET_RetrievalEval.forward(typ='feat') (eval_retrieval.py:100-110) in eval mode, nothing kept on a tape: img f32 (B, Clips, T,
+        3, H, W), txt / mask (B, X) -> (video rows bf16 (B, Lv, H) = the mean over the clips of EncVideo (f32 sums), text rows bf16
+        (B, X, H), text key mask u8 (B, X))"""
+        dev, Hd = self.device, self.cfg["hidden"]
+        B, Cl = img.shape[0], img.shape[1]
+        X = txt.shape[1]
+        saved, self.tape = self.tape, NoTape()
+        try:
+            pool, Lv, _ = self.encode(img.reshape(B * Cl, *img.shape[2:]).to(dev, F32).contiguous(), None, txt.to(dev).contiguous(), None, False)
+        finally:
+            self.tape = saved
+        vid = K.clip_mean(pool.t[:B * Cl * Lv], B, Cl, Lv).view(B, Lv, Hd)
+        return vid, pool.t[B * Cl * Lv:].view(B, X, Hd), (mask.to(dev) != 0).to(torch.uint8)
+
+    def _retrieval_logits(self, xv, keymask, nseq, Lq, Lv, out=None):
+        """fusion encoder (last layer for the text [CLS] row only) + `fc` on assembled sequences -> fc logits f32 [nseq] (into `out`)"""
+        Hd = self.cfg["hidden"]
+        _, r = self.go_layers(xv, keymask, nseq, Lq, False, qrow_split=(0, Lv))
+        st = self._cls_hidden(r.t, False)
+        return K.rowdot(st["h"], self.store.p("fc.3.weight", (2 * Hd,)), self.store.p("fc.3.bias"), 1.0, out=out)
+
+    @torch.no_grad()
+    def retrieval_cross(self, feat_img, mask_img, feat_txt, mask_txt):
+        """VIOLET_RetrievalEval.forward(typ='cross') (eval_retrieval.py:112-115) on B aligned (video, text) pairs -> fc logits f32 [B]"""
+        dev, Hd = self.device, self.cfg["hidden"]
+        B, Lv, X = feat_img.shape[0], feat_img.shape[1], feat_txt.shape[1]
+        seq = torch.cat([feat_img.to(dev, BF16), feat_txt.to(dev, BF16)], 1).reshape(B * (Lv + X), Hd).contiguous()
+        km = torch.cat([mask_img.to(dev) != 0, mask_txt.to(dev) != 0], 1).to(torch.uint8).contiguous()
+        saved, self.tape = self.tape, NoTape()
+        try:
+            return self._retrieval_logits(V(seq), km, B, Lv + X, Lv)
+        finally:
+            self.tape = saved
+
+    @torch.no_grad()
+    def retrieval_corpus_scores(self, vid_bank, txt_bank, txt_mask, gt, max_rows=RETRIEVAL_MAX_ROWS):
+        """Every (text, video) pair of the corpus through the fusion encoder and `fc` (eval_retrieval_tsv.py:60-77), block by block on
+        the device: vid_bank bf16 (Nv, Lv, H), txt_bank bf16 (Nt, X, H), txt_mask (Nt, X), gt = bank index of each text's video.
+        A block (plan_retrieval_blocks) is assembled from the banks by one kernel, runs the layers in their inference form (no tape,
+        no GELU' codes, the last layer on the [CLS] row only) and writes its logits into its run of the score matrix.  Then one launch
+        takes the sigmoid in place and ranks each text's video.  -> (scores f32 (Nt, Nv) on the device, ranks int32 [Nt] on the host)"""
+        dev, Hd = self.device, self.cfg["hidden"]
+        Nv, Lv, _ = vid_bank.shape
+        Nt, X, _ = txt_bank.shape
+        Lq = Lv + X
+        blocks = plan_retrieval_blocks(Nt, Nv, Lq, max_rows)
+        vid_bank, txt_bank = vid_bank.to(dev, BF16).contiguous(), txt_bank.to(dev, BF16).contiguous()
+        txt_mask = (txt_mask.to(dev) != 0).to(torch.uint8).contiguous()
+        gt_d = torch.as_tensor(np.asarray(gt, dtype=np.int32)).to(dev)
+        if gt_d.numel() != Nt:
+            raise ValueError(f"gt holds {gt_d.numel()} entries for {Nt} texts")
+        Pmax = max(nt * nv for _, nt, _, nv in blocks)
+        seq_buf = torch.empty((Pmax * Lq, Hd), device=dev, dtype=BF16)
+        km_buf = torch.empty((Pmax, Lq), device=dev, dtype=torch.uint8)
+        scores = torch.empty((Nt, Nv), device=dev, dtype=F32)
+        flat = scores.view(-1)
+        saved, self.tape = self.tape, NoTape()
+        try:
+            for t0, nt, v0, nv in blocks:
+                P = nt * nv
+                seq, km = seq_buf[:P * Lq], km_buf[:P]
+                K.retrieval_assemble(vid_bank, txt_bank, txt_mask, t0, nt, v0, nv, seq, km)
+                o = t0 * Nv + v0
+                self._retrieval_logits(V(seq), km, P, Lq, Lv, out=flat[o:o + P])
+        finally:
+            self.tape = saved
+        ranks = K.retrieval_rank(scores, gt_d)
+        return scores, ranks.cpu()
 
     # -------------------------------------------------------------- downstream: open-ended video QA (SURVEY 8f.4)
     def qaoe_forward_backward(self, img, txt, mask, ans, train=True, backward=True, dp_all=None):

@@ -10,7 +10,7 @@ import torch
 from . import config as CFG
 from . import kernels as K
 from . import swin_index as SI
-from .store import BF16, F32, V, DropScale, _acc, _gout, _h2d, _dev_i32
+from .store import BF16, F32, V, DropScale, NoTape, _acc, _gout, _h2d, _dev_i32
 
 
 class BertPlan:
@@ -158,10 +158,12 @@ class FusionMixin:
         e = torch.empty
         qkv, ctx, lse = e((M, 3 * Hd), device=dev, dtype=BF16), e((M, Hd), device=dev, dtype=BF16), e((nseq, nh, Lq), device=dev, dtype=F32)
         a, x1, mean1, rstd1 = e((M, Hd), device=dev, dtype=BF16), e((M, Hd), device=dev, dtype=BF16), e(M, device=dev, dtype=F32), e(M, device=dev, dtype=F32)
-        u, h = e((M, F), device=dev, dtype=torch.uint8 if c8 else BF16), e((M, F), device=dev, dtype=BF16)
+        # inference form (a tape that keeps nothing: no backward will read them): the FFN-in epilogue stores no GELU' codes
+        u = None if isinstance(self.tape, NoTape) else e((M, F), device=dev, dtype=torch.uint8 if c8 else BF16)
+        h = e((M, F), device=dev, dtype=BF16)
         f, x2, mean2, rstd2 = e((M, Hd), device=dev, dtype=BF16), e((M, Hd), device=dev, dtype=BF16), e(M, device=dev, dtype=F32), e(M, device=dev, dtype=F32)
         d.x, d.qkv, d.ctx, d.lse, d.a, d.x1, d.mean1, d.rstd1 = (t_.data_ptr() for t_ in (x, qkv, ctx, lse, a, x1, mean1, rstd1))
-        d.u, d.code8, d.h, d.f, d.x2, d.mean2, d.rstd2 = u.data_ptr(), int(c8), h.data_ptr(), f.data_ptr(), x2.data_ptr(), mean2.data_ptr(), rstd2.data_ptr()
+        d.u, d.code8, d.h, d.f, d.x2, d.mean2, d.rstd2 = L.ptr(u), int(c8), h.data_ptr(), f.data_ptr(), x2.data_ptr(), mean2.data_ptr(), rstd2.data_ptr()
         d.keymask, d.causal_from, d.att_colsum = L.ptr(keymask), causal_from, L.ptr(att_out)
         d.off_attn, d.drop_mask, d.off_1, d.off_2 = P.off_attn, L.ptr(P.drop_mask), P.off_1, P.off_2
         d.p_hidden, d.p_attn, d.seed = p_h, p_a, self.seed
@@ -305,9 +307,12 @@ class FusionMixin:
     def go_cross(self, pool, idx, keymask, nseq, Lq, train, causal_from=0, att_out=None, qrow_split=None, mid_hook=False):
         """gather the [img;txt] sequences from the token pool and run the 12 fusion layers (model.py:204-214).
         causal_from = Lv: the seq2seq mask of the smtm pass (main_pretrain.py:217-224, model.py:191-199)."""
-        Hd = self.cfg["hidden"]
-        x = K.gather_rows(pool.t, idx, nseq * Lq)
-        xv = V(x)
+        xv = V(K.gather_rows(pool.t, idx, nseq * Lq))
+        return self.go_layers(xv, keymask, nseq, Lq, train, causal_from, att_out, qrow_split, mid_hook), xv, idx
+
+    def go_layers(self, xv, keymask, nseq, Lq, train, causal_from=0, att_out=None, qrow_split=None, mid_hook=False):
+        """the fusion layers of `go_cross` on already assembled sequences xv = V([nseq * Lq, H]) -> the last layer's output V, or with
+        qrow_split the pair (out_a, out_b) of its two halves (out_a None when n1 == 0)"""
         cur = xv
         nl = self.cfg["bert_layers"]
         for l in range(nl - 1 if qrow_split is not None else nl):
@@ -317,13 +322,13 @@ class FusionMixin:
                 self.tape.append(lambda: self.on_fusion_mid_ready() if self.on_fusion_mid_ready is not None else None)
             cur = self._bert_layer(cur, nseq, Lq, keymask, l, train, causal_from, att_out)
         if qrow_split is None:
-            return cur, xv, idx
+            return cur
         # last layer: the first n1 sequences in full, of the others only the row at `qpos` (see _bert_layer_qrow)
         n1, qpos = qrow_split
         if causal_from != 0 or att_out is not None:     # _bert_layer_qrow has neither the seq2seq mask nor the attention capture
             raise RuntimeError("go_cross(qrow_split=...) serves the plain key-mask pass only (no causal_from / att_out)")
         if n1 == 0:                               # every sequence: only the row at `qpos` (retrieval / open-ended QA read the text [CLS] state only)
-            return (None, self._bert_layer_qrow(cur, nseq, Lq, qpos, keymask, nl - 1, train)), xv, idx
+            return None, self._bert_layer_qrow(cur, nseq, Lq, qpos, keymask, nl - 1, train)
         gbuf = torch.empty_like(cur.t)                                         # d(layer input): the two halves' backward write their rows side by side
         xa = V(cur.t[:n1 * Lq], gbuf[:n1 * Lq])
         xb = V(cur.t[n1 * Lq:], gbuf[n1 * Lq:])
@@ -334,7 +339,7 @@ class FusionMixin:
         self.tape.append(join)
         out_a = self._bert_layer(xa, n1, Lq, keymask[:n1], nl - 1, train, causal_from, att_out)
         out_b = self._bert_layer_qrow(xb, nseq - n1, Lq, qpos, keymask[n1:], nl - 1, train)
-        return (out_a, out_b), xv, idx
+        return out_a, out_b
 
     @torch.no_grad()
     def get_att(self, img, txt, mask, train=True, dp_all=None, cov=None):

@@ -398,9 +398,11 @@ def feature_l1(pred, target, cov, mask_sum, loss_sum, inv_div=1.0 / 3.0):
     return dpred
 
 
-def rowdot(hid, w, b, inv_temp):
+def rowdot(hid, w, b, inv_temp, out=None):
+    """out (optional): f32 [M] destination, e.g. a contiguous slice of a larger score matrix"""
     M, K = hid.shape
-    out = torch.empty(M, device=hid.device, dtype=F32)
+    out = torch.empty(M, device=hid.device, dtype=F32) if out is None else out
+    assert out.dtype == F32 and out.is_contiguous() and out.numel() == M
     L.check(L.load().vmvm_rowdot(hid.data_ptr(), M, K, w.data_ptr(), b.data_ptr(), inv_temp, out.data_ptr(), L.stream()), "rowdot")
     return out
 
@@ -439,6 +441,36 @@ def gather_rows(src, idx, M, rows_out_per_batch=0, rows_in_per_batch=0, out=None
     L.check(L.load().vmvm_gather_rows_bf16(src.data_ptr(), _ld(src), idx.data_ptr(), dst.data_ptr(), Cc, M, Cc, rows_out_per_batch,
                                            rows_in_per_batch, L.stream()), "gather_rows")
     return dst
+
+
+def clip_mean(src, B, clips, rows, out=None):
+    """bf16 [B * clips * rows, H] (clip c of item b = rows (b * clips + c) * rows ...) -> bf16 [B * rows, H], the mean over the clips"""
+    H = src.shape[-1]
+    dst = torch.empty((B * rows, H), device=src.device, dtype=BF16) if out is None else out
+    assert src.is_contiguous() and dst.is_contiguous() and src.numel() == B * clips * rows * H and dst.numel() == B * rows * H
+    L.check(L.load().vmvm_clip_mean_bf16(src.data_ptr(), dst.data_ptr(), B, clips, rows, H, L.stream()), "clip_mean")
+    return dst
+
+
+def retrieval_assemble(vid_bank, txt_bank, txt_mask, t0, nt, v0, nv, seq, keymask):
+    """pair block texts [t0, t0+nt) x videos [v0, v0+nv) -> seq bf16 [nt*nv*Lq, H], keymask u8 [nt*nv, Lq] (include/vmvm.h)"""
+    Nv, Lv, H = vid_bank.shape
+    Nt, X, _ = txt_bank.shape
+    P, Lq = nt * nv, Lv + X
+    assert vid_bank.is_contiguous() and txt_bank.is_contiguous() and txt_mask.is_contiguous() and txt_mask.dtype == torch.uint8
+    assert tuple(txt_mask.shape) == (Nt, X) and seq.numel() >= P * Lq * H and keymask.numel() >= P * Lq
+    L.check(L.load().vmvm_retrieval_assemble(vid_bank.data_ptr(), Nv, Lv, txt_bank.data_ptr(), txt_mask.data_ptr(), Nt, X, H, t0, nt, v0, nv,
+                                             seq.data_ptr(), keymask.data_ptr(), L.stream()), "retrieval_assemble")
+    return seq, keymask
+
+
+def retrieval_rank(scores, gt):
+    """scores f32 (Nt, Nv): fc logits in, sigmoid out (in place); gt int32 [Nt] on the device -> int32 [Nt] ranks (1-based)"""
+    Nt, Nv = scores.shape
+    assert scores.dtype == F32 and scores.stride(1) == 1 and gt.dtype == torch.int32 and gt.numel() == Nt
+    rank = torch.empty(Nt, device=scores.device, dtype=torch.int32)
+    L.check(L.load().vmvm_retrieval_rank(scores.data_ptr(), Nt, Nv, scores.stride(0), gt.data_ptr(), rank.data_ptr(), L.stream()), "retrieval_rank")
+    return rank
 
 
 def pool_grad(g1, g2, g3, B, O, Lv, X, txt_off, txt_list):

@@ -169,6 +169,10 @@ _PROTOS = {
     "vmvm_bert_layer_fwd": ([C.POINTER(BertLayer), c_void_p], c_int),
     "vmvm_bert_layer_bwd": ([C.POINTER(BertLayer), c_void_p, c_void_p, c_void_p], c_int),
     "vmvm_probe_tr16": ([c_void_p, c_void_p], c_int),
+    "vmvm_clip_mean_bf16": ([c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p], c_int),
+    "vmvm_retrieval_assemble": ([c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                c_void_p], c_int),
+    "vmvm_retrieval_rank": ([c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p], c_int),
     # workspace-size queries: the caller owns every buffer, scratch included
     "vmvm_gemm_workspace_size": ([C.POINTER(GemmDesc)], c_i64),
     "vmvm_layernorm_bwd_workspace_size": ([C.POINTER(LnBwdDesc)], c_i64),

@@ -215,6 +215,13 @@ class V:
         self.t, self.g, self.gdst = t, None, gdst
 
 
+class NoTape(list):
+    """a tape that keeps nothing: the engine's blocks push their backward closures here and they are dropped (and with them the
+    activations they hold) -- frozen teachers and the inference passes of the retrieval evaluation"""
+    def append(self, fn):
+        pass
+
+
 class DropScale:
     """One DropPath draw of a Swin block branch (video_swin.py:46-54): dev = f32 (B,) scales (0 or 1 / keep) on the device; host = the same
     on the host (which clips were dropped is known WITHOUT a device round trip: the draw happens on the host); kept / dropped = int32

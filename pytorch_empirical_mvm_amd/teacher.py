@@ -15,13 +15,8 @@ import torch
 
 from . import config as CFG
 from .engine import ParamStore, VioletEngine
+from .store import NoTape
 from .switches import Switches
-
-
-class _NoTape(list):
-    """the engine's blocks push their backward closures here; a frozen teacher drops them (and with them the activations)"""
-    def append(self, fn):
-        pass
 
 
 class SwinTeacher:
@@ -118,7 +113,7 @@ class SwinTeacher:
         main_pretrain.py:518 / :537."""
         B, T, _, H, W = img.shape
         eng = self.eng
-        eng.tape = _NoTape()
+        eng.tape = NoTape()                          # a frozen teacher drops its backward closures
         if self.kind == "3d":
             out, dims, C = eng.swin_forward(img, None, None)
         else:

@@ -158,6 +158,34 @@ def main(verbose=True):
     expect("bert_layer_bwd: sizes but no buffers", l.vmvm_bert_layer_bwd(C.byref(bl), None, None, None), EINVAL)
     bl.hidden = 770
     expect("bert_layer_fwd: hidden not a multiple of the head count", l.vmvm_bert_layer_fwd(C.byref(bl), None), EINVAL)
+    # u == NULL is the forward's inference form (no GELU' codes stored) and is refused by the backward, which reads them: with every
+    # other buffer set, the forward passes its checks and reaches the first GEMM, which refuses the 2^28-row problem (ENOSUPPORT,
+    # before any launch) -- the backward stops at u (EINVAL)
+    bu = lib.BertLayer()
+    bu.nseq, bu.L, bu.hidden, bu.heads, bu.ffn = 1 << 20, 256, 768, 12, 3072
+    for f_ in ("Wqkv", "Wo", "W1", "W2", "bqkv", "bo", "b1", "b2", "ln1_g", "ln1_b", "ln2_g", "ln2_b", "x", "qkv", "ctx", "lse", "a", "x1",
+               "mean1", "rstd1", "h", "f", "x2", "mean2", "rstd2", "gWqkv", "gWo", "gW1", "gW2", "gbqkv", "gbo", "gb1", "gb2", "gln1_g",
+               "gln1_b", "gln2_g", "gln2_b", "d_out", "d_x", "df", "du", "dx1", "da", "dctx", "dqkv", "delta"):
+        setattr(bu, f_, p)
+    bu.u = None
+    expect("bert_layer_fwd: u = NULL accepted (inference form)", l.vmvm_bert_layer_fwd(C.byref(bu), None), ENOSUPPORT)
+    expect("bert_layer_bwd: u = NULL refused", l.vmvm_bert_layer_bwd(C.byref(bu), None, None, None), EINVAL)
+    bu.u = p
+    expect("bert_layer_fwd: u set, same problem", l.vmvm_bert_layer_fwd(C.byref(bu), None), ENOSUPPORT)
+    # ---- retrieval evaluation (csrc/retrieval.hip)
+    expect("clip_mean_bf16: null", l.vmvm_clip_mean_bf16(z, z, 1, 2, 8, 768, z), EINVAL)
+    expect("clip_mean_bf16: H not a multiple of 8", l.vmvm_clip_mean_bf16(p, p, 1, 2, 8, 100, z), EINVAL)
+    expect("clip_mean_bf16: zero clips", l.vmvm_clip_mean_bf16(p, p, 1, 0, 8, 768, z), EINVAL)
+    expect("clip_mean_bf16: beyond 2^40 elements", l.vmvm_clip_mean_bf16(p, p, 1 << 20, 64, 1 << 10, 768, z), ENOSUPPORT)
+    expect("retrieval_assemble: null", l.vmvm_retrieval_assemble(z, 4, 8, z, z, 4, 8, 768, 0, 1, 0, 4, z, z, z), EINVAL)
+    expect("retrieval_assemble: text block outside the bank", l.vmvm_retrieval_assemble(p, 4, 8, p, p, 4, 8, 768, 3, 2, 0, 4, p, p, z), EINVAL)
+    expect("retrieval_assemble: video block outside the bank", l.vmvm_retrieval_assemble(p, 4, 8, p, p, 4, 8, 768, 0, 1, 1, 4, p, p, z), EINVAL)
+    expect("retrieval_assemble: negative start", l.vmvm_retrieval_assemble(p, 4, 8, p, p, 4, 8, 768, -1, 1, 0, 4, p, p, z), EINVAL)
+    expect("retrieval_assemble: H not a multiple of 8", l.vmvm_retrieval_assemble(p, 4, 8, p, p, 4, 8, 100, 0, 1, 0, 4, p, p, z), EINVAL)
+    expect("retrieval_assemble: misaligned bank", l.vmvm_retrieval_assemble(p + 2, 4, 8, p, p, 4, 8, 768, 0, 1, 0, 4, p, p, z), EINVAL)
+    expect("retrieval_rank: null", l.vmvm_retrieval_rank(z, 4, 4, 4, z, z, z), EINVAL)
+    expect("retrieval_rank: ld below Nv", l.vmvm_retrieval_rank(p, 4, 8, 4, p, p, z), EINVAL)
+    expect("retrieval_rank: empty", l.vmvm_retrieval_rank(p, 0, 8, 8, p, p, z), EINVAL)
     sb = lib.SwinBlock()
     for nm in ("vmvm_swin_block_fwd", "vmvm_swin_block_bwd"):
         fn = getattr(l, nm)
