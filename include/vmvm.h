@@ -538,6 +538,21 @@ int vmvm_retrieval_assemble(const void* vid_bank, int32_t Nv, int32_t Lv, const 
  * descending score = 1 + #{v : s > s_gt} + #{v < gt : s == s_gt} (-1 when gt[t] is outside [0, Nv)); one workgroup per row */
 int vmvm_retrieval_rank(float* scores, int32_t Nt, int32_t Nv, int32_t ld, const int32_t* gt, int32_t* rank, void* stream);
 
+/* Video token selection of the fc-head multiple-choice QA model (VIOLET_QAMC.select_vid_token, main_qamc.py:55-83; csrc/qamc.hip).
+ * q, k: bf16 [B*Lv][H] row-major (feat_img times vid_query / vid_key, bias-free); n selection heads of width d = H / n, d in {4, 8, 16}.
+ * Per (clip b, head h): s = q_h k_h^T / sqrt(H) (H, not d), keys with vis_mask == 0 left out of the softmax (every key masked: the
+ * reference's uniform row); c[j] = sum over the query rows of softmax_j(s); dropout(p) on c (the Philox convention of the GEMM
+ * epilogues, element (b*n + h)*Lv + j, stream (seed_drop, off_drop)); then idx[b][h] = argmax_j (c[j] + g[j]), the lowest index on a
+ * tie.  g = noise[b][h][j] (f32 [B][n][Lv]) when noise != NULL, else -log(-log(U)) with U in (0, 1] drawn from Philox4x32-7 at
+ * (seed_noise, off_noise).  sel u8 [B][Lv] = vis_mask AND the union of the clip's n selections (vis_mask NULL: every token live).
+ * No atomics, fixed summation orders: bit-reproducible, and a clip's result does not depend on the other clips of the launch.
+ * Host checks: null q / k / idx / sel, H % n, d outside {4, 8, 16}, Lv > VMVM_VIDEO_TOKEN_SELECT_MAX_LV (q_h and k_h of one clip are
+ * staged in LDS: Lv * (8 + 4 d) bytes, within 64 KiB at d = 16), p outside [0, 1) -> VMVM_EINVAL. */
+#define VMVM_VIDEO_TOKEN_SELECT_MAX_LV 896
+int vmvm_video_token_select(const void* q, const void* k, const uint8_t* vis_mask, const float* noise, int32_t B, int32_t Lv, int32_t H,
+                            int32_t n, float dropout_p, uint64_t seed_drop, uint64_t off_drop, uint64_t seed_noise, uint64_t off_noise,
+                            int32_t* idx, uint8_t* sel, void* stream);
+
 /* hardware probe used by tests: dumps the lane mapping of ds_read_b64_tr_b16 (out: 64*4 int32) */
 int vmvm_probe_tr16(int32_t* out, void* stream);
 

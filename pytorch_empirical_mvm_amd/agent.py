@@ -209,6 +209,11 @@ class Agent_Pretrain:
         lrs = [max(1e-8, base * mul * f), max(1e-8, base * f)]
         return [lrs[0], lrs[1], lrs[0], lrs[1]]
 
+    def segment_runs(self, gi, lrs):
+        """[(a, e, lr)]: the runs of arena segment gi that AdamW updates at one rate each -- here the whole segment at lrs[gi]"""
+        a, e = self.engine.store.segments[gi]
+        return [(a, e, lrs[gi])]
+
     def step(self, batch, is_train=True, negatives=None, dp_all=None, sync=True):
         eng = self.engine
         src_img = batch["unmask_img"] if "unmask_img" in batch else batch["img"]
@@ -312,13 +317,13 @@ class Agent_Pretrain:
 
         def update(groups):
             for gi in groups:
-                ga, ge = S.segments[gi]
-                for oa, oe in own:
-                    a, e = max(ga, oa), min(ge, oe)      # (ZeRO-1: this rank's parts of the group; otherwise the whole group)
-                    if e > a:
-                        K.adamw(S.flat[a:e], S.grad[a:e], S.m[a:e], S.v[a:e], S.shadow[a:e], lr=lrs[gi], weight_decay=(self.args.decay if gi < 2 else 0.0),
-                                beta1=0.9, beta2=0.98, eps=1e-8, step=self.opt_step, sumsq_t=self._sumsq, max_grad_norm=float(self.args.max_grad_norm),
-                                grad_scale=gscale)
+                for ga, ge, lr in self.segment_runs(gi, lrs):
+                    for oa, oe in own:
+                        a, e = max(ga, oa), min(ge, oe)      # (ZeRO-1: this rank's parts of the run; otherwise the whole run)
+                        if e > a:
+                            K.adamw(S.flat[a:e], S.grad[a:e], S.m[a:e], S.v[a:e], S.shadow[a:e], lr=lr, weight_decay=(self.args.decay if gi < 2 else 0.0),
+                                    beta1=0.9, beta2=0.98, eps=1e-8, step=self.opt_step, sumsq_t=self._sumsq, max_grad_norm=float(self.args.max_grad_norm),
+                                    grad_scale=gscale)
         eng = self.engine
         split = getattr(eng, "wstream", None) is not None and eng.sw.opt_overlap and not z1 and getattr(S, "shadow8", None) is None
         if split:

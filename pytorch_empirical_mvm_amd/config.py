@@ -77,7 +77,27 @@ def model_cfg(args):
     cfg["task"] = args.get("task", "pretrain")
     cfg["size_vocab"] = args.get("size_vocab", 0)        # open-ended QA answer vocabulary (main_qaoe.py:47)
     cfg["fp8_forward"] = bool(args.get("fp8_forward", False))     # config 5 ("fp8 MFMA path"): e4m3 forward GEMMs of the fusion qkv / FFN-in, opt-in
+    if cfg["task"] == "qamc":
+        cfg.update(qamc_options(args))
     return cfg
+
+
+NUM_VIDEO_TOKENS = (-1, 48, 96, 192)      # utils/args.py:48 choices (+ the default -1: no token selection)
+
+
+def qamc_options(args):
+    """VIOLET_QAMC's options (utils/args.py:48-49; `size_option` of _args/args_tgif-action.json): num_video_tokens in {-1, 48, 96, 192}, gumble_tau > 0
+    (the hard gumbel-softmax's forward value does not depend on it), size_option = the options per question."""
+    ntok = int(args.get("num_video_tokens", -1))
+    if ntok not in NUM_VIDEO_TOKENS:
+        raise ValueError(f"num_video_tokens must be one of {NUM_VIDEO_TOKENS}, got {ntok}")
+    tau = float(args.get("gumble_tau", 1.0))
+    if not tau > 0:
+        raise ValueError(f"gumble_tau must be > 0, got {tau}")
+    opt = args.get("size_option", 5)
+    if int(opt) < 1:
+        raise ValueError(f"size_option must be >= 1, got {opt}")
+    return dict(num_video_tokens=ntok, gumble_tau=tau, size_option=int(opt))
 
 
 def param_shapes(cfg):
@@ -150,6 +170,11 @@ def param_shapes(cfg):
     s["fc.3.weight"] = (1, 2 * H)
     s["fc.3.bias"] = (1,)
     if cfg.get("task", "pretrain") == "retrieval":       # VIOLET_Retrieval (main_retrieval.py:56-61): VIOLET_Base + fc only
+        return s
+    if cfg.get("task", "pretrain") == "qamc":            # VIOLET_QAMC (main_qamc.py:50-64): VIOLET_Base + fc (+ the token selection's projections)
+        if int(cfg.get("num_video_tokens", -1)) != -1:
+            s["vid_key.weight"] = (H, H)                 # all_head_size = n * (H // n) = H for every allowed n
+            s["vid_query.weight"] = (H, H)
         return s
     if cfg.get("task", "pretrain") == "qaoe":            # VIOLET_QAOE (main_qaoe.py:42-47): fc ends in Linear(2H, size_vocab)
         s["fc.3.weight"] = (int(cfg["size_vocab"]), 2 * H)

@@ -6,6 +6,9 @@
   device, R@1/5/10 and the median rank.
 * Open-ended video QA: `VIOLET_QAOE` / `Agent_QAOE` (main_qaoe.py:42-90) -- one (video, question) pass, classification over the
   answer vocabulary on the text [CLS] state.
+* Multiple-choice video QA, fc-head form: `VIOLET_QAMC` / `Agent_QAMC` (main_qamc.py:50-155) -- one "question + option" sequence per
+  option, the clip's video tokens shared by its options, `fc` scores each option at the text [CLS] state, cross entropy over the
+  options; `num_video_tokens` in {48, 96, 192} first keeps the union of that many selection heads' gumbel arg-max video tokens.
 * Multiple-choice video QA, MLM-head form: `VIOLET_QAMC_MLM_Head` / `Agent_QAMC_MLM_Head` (main_qamc_tsv_mlm_head.py:61-123) -- one
   "question + option + [MASK]" sequence per option, the clip's video tokens shared by its options, the pre-training MLM head
   predicts the true / false token at [MASK].
@@ -14,6 +17,8 @@
   `VIOLET_QAOE_LSMDC` / `Agent_QAOE_LSMDC` = `Agent_QAOE_MLM_Head` (main_qaoe_lsmdc_fib.py:55-115, main_qaoe_tsv_mlm_head.py:101-130:
   top-1 / top-5 accuracy).
 Same encoders, token pool and fusion kernels as pre-training; checkpoints interchange through the shared key names."""
+import math
+
 import torch
 
 from . import config as CFG
@@ -158,6 +163,79 @@ class Agent_QAOE(Agent_Pretrain):
             return float(loss.item())
         _, logits = eng.qaoe_forward_backward(img, txt, mask, ans, train=False, backward=False)
         return (logits.argmax(1) == ans.to(dev)).float().tolist()
+
+
+class VIOLET_QAMC(VIOLET_Pretrain):
+    """VIOLET_Base + `fc` (Dropout, Linear(768, 1536), ReLU, Linear(1536, 1)) (+ `vid_key` / `vid_query`, bias-free Linear(768, 768), when
+    num_video_tokens != -1)   (main_qamc.py:50-64).  Checkpoint keys enc_img.* / enc_txt.* / trsfr.* / fc.* (/ vid_key.weight /
+    vid_query.weight); a pre-training checkpoint loads through `load_ckpt` and leaves fc / vid_* at their initial values."""
+
+    def __init__(self, args, tokzr=None, device="cuda"):
+        args = CFG.Args(dict(args))
+        args.update(task="qamc", mvm_target=[])
+        args.update(CFG.qamc_options(args))
+        super().__init__(args, tokzr, device=device)
+
+    @torch.no_grad()
+    def forward(self, img, txt, mask, ans):
+        """img (B, T, 3, H, W), txt / mask (B, O, X), ans (B,) -> (out (B, O) f32 = fc at each option's text [CLS], ans)   (:85-98)"""
+        dev = self.engine.device
+        r = self.engine.qamc_forward_backward(img.to(dev, torch.float32).contiguous(), txt.to(dev).contiguous(), mask.to(dev).contiguous(),
+                                              ans.to(dev), train=self.training, backward=False)
+        return r[1], ans
+
+    @torch.no_grad()
+    def reinit_head(self):
+        """main_qamc.py:100-103: a fresh `fc` with nn.Linear's default initialisation (weight and bias U(+-1/sqrt(fan_in)), torch's global
+        generator, as the reference's module constructor draws)"""
+        S = self.engine.store
+        S.sync_pending()
+        for name in ("fc.1.weight", "fc.1.bias", "fc.3.weight", "fc.3.bias"):
+            fan_in = self.hidden_size if name.startswith("fc.1.") else 2 * self.hidden_size
+            b = 1.0 / math.sqrt(fan_in)
+            S.p(name).copy_(torch.empty(S.index[name][2]).uniform_(-b, b).to(S.device))
+        S.refresh_shadow()
+
+
+class Agent_QAMC(Agent_Pretrain):
+    """Agent_QAMC (main_qamc.py:105-155).  step: train -> CrossEntropyLoss over the options + the shared backward_step (all-reduce, clip,
+    AdamW, schedule); eval -> per-clip correctness of the arg-max option.  Optimizer groups (build_optimizer :111-140): the
+    `vis_backbone_lr_mul` groups are the parameters named `fc.*` (NOT the Video-Swin backbone, despite the variable names), everything
+    else runs at the base rate; vid_key / vid_query never get a gradient, so AdamW skips them (no update, no decay)."""
+
+    def __init__(self, args, model):
+        super().__init__(args, model)
+        S = self.engine.store
+        self._fc_tail = {gi: S.tail_start(gi, "fc.") for gi in (1, 3)}        # fc.* = the tail of the two non-Swin segments (asserted)
+        self.log = {"ls_tr": [], "ac_vl": [], "ac_ts": []}
+
+    def current_lrs(self):
+        """the reference's four groups in its order: [fc decay, other decay, fc no-decay, other no-decay]"""
+        f = CFG.lr_factor(self.sched_step, self.args.max_iter)
+        fc, other = max(1e-8, self.args.lr * self.args.vis_backbone_lr_mul * f), max(1e-8, self.args.lr * f)
+        return [fc, other, fc, other]
+
+    def segment_runs(self, gi, lrs):
+        """arena segment gi (0 / 2: Swin, 1 / 3: the rest, decay / no-decay) -> runs at the base rate, then fc.* at the multiplied one"""
+        a, e = self.engine.store.segments[gi]
+        base, fc = (lrs[1], lrs[0]) if gi < 2 else (lrs[3], lrs[2])
+        t = self._fc_tail.get(gi, e)
+        return [r for r in ((a, t, base), (t, e, fc)) if r[1] > r[0]]
+
+    def step(self, img, txt, mask, ans, is_train=True):
+        eng = self.engine
+        dev = eng.device
+        img, txt, mask = img.to(dev, torch.float32).contiguous(), txt.to(dev).contiguous(), mask.to(dev).contiguous()
+        ans = ans.to(dev)
+        if is_train:
+            loss = eng.qamc_forward_backward(img, txt, mask, ans, train=True, backward=True)[0]
+            if self.comm is not None:
+                self.comm.reduce_other()
+            self.backward_step()
+            self.global_step += 1
+            return float(loss.item())
+        logits = eng.qamc_forward_backward(img, txt, mask, ans, train=False, backward=False)[1]
+        return (logits.argmax(1) == ans).float().tolist()
 
 
 class VIOLET_QAMC_MLM_Head(VIOLET_Pretrain):

@@ -60,10 +60,11 @@ class DownstreamMixin:
         X = txt.shape[1]
         return pool, Lv, X, Lv + X
 
-    def _fuse_pairs(self, pool, key, pairs, B, mask, Lv, X, train, cls_only):
+    def _fuse_pairs(self, pool, key, pairs, B, mask, Lv, X, train, cls_only, vis_mask=None):
         """One fusion pass over the (clip i, text sequence j) pairs: rows gathered from the token pool, key mask = ones over the visual part
-        + the text's mask.  cls_only: the head reads the text [CLS] state alone, so the last layer runs for that query row only
-        (`go_cross(qrow_split=(0, Lv))`).  -> dict(out = V of the full output or of the [CLS] rows, inn, idx, n_closures)."""
+        (or clip i's row of `vis_mask`, u8 (B, Lv)) + the text's mask.  cls_only: the head reads the text [CLS] state alone, so the last
+        layer runs for that query row only (`go_cross(qrow_split=(0, Lv))`).  -> dict(out = V of the full output or of the [CLS] rows,
+        inn, idx, n_closures)."""
         dev = self.device
         ar_v, ar_t = np.arange(Lv), np.arange(X)
         idx_d = self._cached(key, lambda: _dev_i32(np.concatenate([np.concatenate([i * Lv + ar_v, B * Lv + j * X + ar_t]) for i, j in pairs]), dev))
@@ -71,7 +72,12 @@ class DownstreamMixin:
         tj = [j for _, j in pairs]
         if tj != list(range(km_txt.shape[0])):
             km_txt = km_txt[_h2d(torch.tensor(tj), dev)]
-        km = torch.cat([torch.ones(len(pairs), Lv, dtype=torch.uint8, device=dev), km_txt], 1).contiguous()
+        if vis_mask is None:
+            km_vis = torch.ones(len(pairs), Lv, dtype=torch.uint8, device=dev)
+        else:
+            ci = self._cached(("pair_clips",) + tuple(key), lambda: _h2d(torch.tensor([i for i, _ in pairs]), dev))
+            km_vis = vis_mask.index_select(0, ci)
+        km = torch.cat([km_vis, km_txt], 1).contiguous()
         ntape = len(self.tape)
         if cls_only:
             (_, out), inn, _ = self.go_cross(pool, idx_d, km, len(pairs), Lv + X, train, qrow_split=(0, Lv))
@@ -260,3 +266,58 @@ class DownstreamMixin:
         inv = self._cached(("qamc_inv", n_seq, Lq, Lv, X), lambda: self._inverse_rows(n_seq * Lq, [txt_rows]))
         self._finish_pass(fz, pool, K.gather_rows(dtxt, inv, n_seq * Lq))
         return loss, lg_[:, :Vv]
+
+    # -------------------------------------------------------------- downstream: multiple-choice video QA, fc-head form
+    def _select_video_tokens(self, vis, B, Lv, n, train, noise=None):
+        """VIOLET_QAMC.select_vid_token (main_qamc.py:66-83) on the B clips' visual rows vis bf16 [B*Lv, H]: the two bias-free projections
+        (vid_query, vid_key), then vmvm_video_token_select with vid_dropout (0.1, train only) and the gumbel noise (drawn in eval too, as
+        the reference does; `noise` f32 (B, n, Lv) replaces the draw).  The reference's mask_img is all ones on this video path, so no
+        visual mask is passed (NULL = every token live).  -> u8 (B, Lv) context mask.  q / k / idx / sel stay in `self.qamc_select`
+        until the next pass (tests read them).  No backward: the hard `> 0` passes no gradient to vid_key / vid_query."""
+        S, dev = self.store, self.device
+        q = K.gemm(vis, S.b("vid_query.weight"))
+        k = K.gemm(vis, S.b("vid_key.weight"))
+        p = 0.1 if train else 0.0
+        off_d = self._next_offset(B * n * Lv) if p > 0 else 0
+        off_n = self._next_offset(B * n * Lv) if noise is None else 0
+        if noise is not None:
+            noise = noise.to(dev, F32).contiguous()
+        idx, sel = K.video_token_select(q, k, B, Lv, n, vis_mask=None, noise=noise, dropout_p=p, seed_drop=self.seed, off_drop=off_d,
+                                        seed_noise=self.seed, off_noise=off_n)
+        self.qamc_select = dict(q=q, k=k, idx=idx, sel=sel)
+        return sel
+
+    def qamc_forward_backward(self, img, txt, mask, ans, train=True, backward=True, dp_all=None, noise=None, dlogits=None):
+        """VIOLET_QAMC.forward + Agent_QAMC.step (main_qamc.py:85-98,142-155): txt / mask (B, O, X) = one sequence per option, ans (B,)
+        the true option.  The B clips and the B*O option texts are encoded once; with num_video_tokens != -1 the clips' visual rows go
+        through the token selection first and its mask becomes the visual part of the key mask.  The clip's video tokens are shared by
+        its O sequences (B*O pairs gathered from one token pool), the last fusion layer runs for the text [CLS] row only, `fc` scores
+        each option there, cross entropy over the O options.  Returns (loss f32[1], logits (B, O) f32) and, with the selection on, its
+        context mask u8 (B, Lv) as a third element.  `dlogits` (B, O) f32 replaces d(loss)/d(logits) in the backward (tests: as
+        retrieval_forward_backward's, a probe of the backward path that does not cancel across the options)."""
+        cfg, S, dev = self.cfg, self.store, self.device
+        B, O, Hd = img.shape[0], int(txt.shape[1]), cfg["hidden"]
+        n_seq = B * O
+        txt2, mask2 = txt.reshape(n_seq, -1).contiguous(), mask.reshape(n_seq, -1).contiguous()
+        pool, Lv, X, Lq = self._begin_pass(img, txt2, train, dp_all)          # pool rows: B*Lv visual, then (B*O)*X text
+        ntok = int(cfg.get("num_video_tokens", -1))
+        sel = self._select_video_tokens(pool.t[:B * Lv], B, Lv, ntok, train, noise) if ntok != -1 else None
+        fz = self._fuse_pairs(pool, ("qamc_fc_idx", B, O, Lv, X), [(s_ // O, s_) for s_ in range(n_seq)], B, mask2, Lv, X, train,
+                              cls_only=True, vis_mask=sel)
+        st = self._cls_hidden(fz["out"].t, train)
+        logits = K.rowdot(st["h"], S.p("fc.3.weight", (2 * Hd,)), S.p("fc.3.bias"), 1.0).view(B, O)
+        loss = torch.zeros(1, device=dev, dtype=F32)
+        tgt = ans.to(dev, torch.int64).reshape(-1).contiguous()
+        K.cross_entropy(logits, O, tgt, loss, want_grad=False)
+        ret = (loss, logits) if sel is None else (loss, logits, sel)
+        if not backward:
+            self.tape = []
+            return ret
+        # d(loss)/d(logits) in f32 (tiny (B, O) matrix: plumbing).  A clip's O entries sum to zero and its O sequences share the video
+        # rows: a bf16-rounded row leaves a residual that multiplies the options' common gradient and buries the signal (as for VTM)
+        dlg = ((torch.softmax(logits, 1) - torch.nn.functional.one_hot(tgt, O).to(F32)) / B).reshape(-1).contiguous()
+        if dlogits is not None:
+            dlg = dlogits.to(dev, F32).reshape(-1).contiguous()
+        dh = K.rowdot_bwd(st["h"], S.p("fc.3.weight", (2 * Hd,)), dlg, 1.0, S.g("fc.3.weight", (2 * Hd,)), S.g("fc.3.bias"), relu_mask=True)
+        self._finish_pass(fz, pool, self._cls_hidden_bwd(st, dh))
+        return ret

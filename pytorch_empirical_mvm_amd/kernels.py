@@ -473,6 +473,27 @@ def retrieval_rank(scores, gt):
     return rank
 
 
+VIDEO_TOKEN_SELECT_MAX_LV = 896        # include/vmvm.h VMVM_VIDEO_TOKEN_SELECT_MAX_LV
+
+
+def video_token_select(q, k, B, Lv, n, vis_mask=None, noise=None, dropout_p=0.0, seed_drop=0, off_drop=0, seed_noise=0, off_noise=0):
+    """VIOLET_QAMC.select_vid_token (include/vmvm.h): q / k bf16 [B*Lv, H] -> (idx int32 (B, n) = each head's selected token,
+    sel u8 (B, Lv) = vis_mask AND the union of the selections).  vis_mask u8 (B, Lv) or None; noise f32 (B, n, Lv) replaces the draw."""
+    H = q.shape[-1]
+    assert q.dtype == BF16 and k.dtype == BF16 and q.is_contiguous() and k.is_contiguous()
+    assert q.numel() == B * Lv * H and k.numel() == B * Lv * H
+    if vis_mask is not None:
+        assert vis_mask.dtype == torch.uint8 and vis_mask.is_contiguous() and vis_mask.numel() == B * Lv
+    if noise is not None:
+        assert noise.dtype == F32 and noise.is_contiguous() and noise.numel() == B * n * Lv
+    idx = torch.empty((B, n), device=q.device, dtype=torch.int32)
+    sel = torch.empty((B, Lv), device=q.device, dtype=torch.uint8)
+    L.check(L.load().vmvm_video_token_select(q.data_ptr(), k.data_ptr(), L.ptr(vis_mask), L.ptr(noise), B, Lv, H, n, float(dropout_p),
+                                             int(seed_drop), int(off_drop), int(seed_noise), int(off_noise), idx.data_ptr(), sel.data_ptr(),
+                                             L.stream()), "video_token_select")
+    return idx, sel
+
+
 def pool_grad(g1, g2, g3, B, O, Lv, X, txt_off, txt_list):
     """gradient of the token pool from the gradients of the gathered pass-1 / pass-2 (/ smtm) sequences (include/vmvm.h)"""
     Hd = g1.shape[1]

@@ -173,6 +173,8 @@ _PROTOS = {
     "vmvm_retrieval_assemble": ([c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                 c_void_p], c_int),
     "vmvm_retrieval_rank": ([c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p], c_int),
+    "vmvm_video_token_select": ([c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_u64, c_u64, c_u64, c_u64,
+                                c_void_p, c_void_p, c_void_p], c_int),
     # workspace-size queries: the caller owns every buffer, scratch included
     "vmvm_gemm_workspace_size": ([C.POINTER(GemmDesc)], c_i64),
     "vmvm_layernorm_bwd_workspace_size": ([C.POINTER(LnBwdDesc)], c_i64),

@@ -20,7 +20,8 @@ BF16, F32 = torch.bfloat16, torch.float32
 class ParamStore:
     """All parameters in ONE flat f32 buffer (+ grad, Adam m/v, bf16 compute copy), laid out by optimizer
     group (agent.py:84-113) so clip / AdamW / all-reduce are a handful of launches over contiguous memory."""
-    FROZEN = ("enc_img.emb_odr", "emb_task")   # never receive a gradient on the built paths (SURVEY section 9; emb_task: task token off)
+    FROZEN = ("enc_img.emb_odr", "emb_task",   # never receive a gradient on the built paths (SURVEY section 9; emb_task: task token off;
+              "vid_key.weight", "vid_query.weight")     # VIOLET_QAMC's token selection: its hard `> 0` test passes no gradient, main_qamc.py:80-82)
     PAD = 16                 # elements: bf16 views 32-byte, fp8 views 16-byte aligned (DMA chunks)
     TAIL = 1 << 16
 
@@ -79,6 +80,18 @@ class ParamStore:
             if all(is_tail(n) for n in names if self.index[n][0] >= split):
                 out.append((split, e))
         return out
+
+    def tail_start(self, gi, prefix):
+        """offset where the parameters named `prefix*` begin in optimizer segment gi, asserted to be the segment's tail: every parameter of
+        the segment from there on carries the prefix and none before it does (segment end when the segment holds none)"""
+        a, e = self.segments[gi]
+        names = sorted((o, n) for n, (o, c, _) in self.index.items() if a <= o < e)
+        own = [o for o, n in names if n.startswith(prefix)]
+        if not own:
+            return e
+        split = min(own)
+        assert all(n.startswith(prefix) == (o >= split) for o, n in names), f"`{prefix}*` is not the tail of segment {gi}"
+        return split
 
     def _view(self, buf, n, shape=None):
         o, c, s = self.index[n]

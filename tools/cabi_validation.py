@@ -186,6 +186,20 @@ def main(verbose=True):
     expect("retrieval_rank: null", l.vmvm_retrieval_rank(z, 4, 4, 4, z, z, z), EINVAL)
     expect("retrieval_rank: ld below Nv", l.vmvm_retrieval_rank(p, 4, 8, 4, p, p, z), EINVAL)
     expect("retrieval_rank: empty", l.vmvm_retrieval_rank(p, 0, 8, 8, p, p, z), EINVAL)
+    # ---- video token selection of the fc-head multiple-choice QA model (csrc/qamc.hip)
+    vts = l.vmvm_video_token_select
+    expect("video_token_select: null q / k", vts(z, z, z, z, 2, 250, 768, 48, 0.1, 1, 0, 1, 0, p, p, z), EINVAL)
+    expect("video_token_select: null idx", vts(p, p, z, z, 2, 250, 768, 48, 0.1, 1, 0, 1, 0, z, p, z), EINVAL)
+    expect("video_token_select: null sel", vts(p, p, z, z, 2, 250, 768, 48, 0.1, 1, 0, 1, 0, p, z, z), EINVAL)
+    expect("video_token_select: H % n != 0", vts(p, p, z, z, 2, 250, 768, 100, 0.1, 1, 0, 1, 0, p, p, z), EINVAL)
+    expect("video_token_select: head width 2 (n = 384)", vts(p, p, z, z, 2, 250, 768, 384, 0.1, 1, 0, 1, 0, p, p, z), EINVAL)
+    expect("video_token_select: head width 32 (n = 24)", vts(p, p, z, z, 2, 250, 768, 24, 0.1, 1, 0, 1, 0, p, p, z), EINVAL)
+    expect("video_token_select: Lv beyond the LDS bound", vts(p, p, z, z, 2, 897, 768, 48, 0.1, 1, 0, 1, 0, p, p, z), EINVAL)
+    expect("video_token_select: p = 1", vts(p, p, z, z, 2, 250, 768, 48, 1.0, 1, 0, 1, 0, p, p, z), EINVAL)
+    expect("video_token_select: p < 0", vts(p, p, z, z, 2, 250, 768, 48, -0.1, 1, 0, 1, 0, p, p, z), EINVAL)
+    expect("video_token_select: p NaN", vts(p, p, z, z, 2, 250, 768, 48, float("nan"), 1, 0, 1, 0, p, p, z), EINVAL)
+    expect("video_token_select: no clips", vts(p, p, z, z, 0, 250, 768, 48, 0.1, 1, 0, 1, 0, p, p, z), EINVAL)
+    expect("video_token_select: misaligned q", vts(p + 1, p, z, z, 2, 250, 768, 48, 0.1, 1, 0, 1, 0, p, p, z), EINVAL)
     sb = lib.SwinBlock()
     for nm in ("vmvm_swin_block_fwd", "vmvm_swin_block_bwd"):
         fn = getattr(l, nm)
